@@ -9,7 +9,10 @@ One step = forward + backward (+ gradient all-reduce over RCCL when N > 1) + Ada
 advance on the configs[1] workload: 2 enc + 2 dec layers, d=512, ff=2048, 8 heads, V=30522, bf16
 compute / fp32 masters, per-GPU batch 256 of synthetic (12 x 512) CLIP4Clip features -> 20-token
 captions, dropout 0.3 active, SCE alpha 0.5.  Inputs are resident in HBM before the timed region.
-Prints ONE JSON line (rank 0)."""
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints the headline (`value`, `ms_per_step`,
+`step_tflops`, ...); `--full` adds the kernel brackets (roofline, north_star, hbm_kernels, comm timings) and the side lines
+(batch 1024, other configs, decode, exchange path at N=1, CPU baseline).  `--dump-outputs DIR` writes what the last timed
+step produced (dump_outputs)."""
 import argparse
 import json
 import os
@@ -57,6 +60,42 @@ def synthetic(B, rank, device):
     ids[:, 0], ids[:, -1] = 101, 102
     mask = torch.zeros(B, T_FRAMES, dtype=torch.bool)
     return feats.to(device), mask.to(device), ids.to(device)
+
+
+DUMP_SAMPLE = 1 << 18       # elements kept of a larger tensor: 69 parameters x 2 arrays stay under 48 MB at configs[1]
+
+
+def dump_outputs(out_dir, model, opt, loss, rank):
+    """What the last step left its caller, as <out_dir>/<name>.npy (float32): `loss`, and per parameter of the caption path its
+    fp32 master (`param.<name>`) and Adam's first moment (`adam_exp_avg.<name>`, a running mean of the gradients).  A tensor of
+    more than DUMP_SAMPLE elements is reduced to the elements at sorted indices drawn from a generator seeded by its name, so
+    two builds are compared on the same positions.  Every rank calls this (the sharded optimizer gathers its moments); rank 0
+    writes."""
+    import zlib
+    from vct_amd.trainer import FusedAdam
+    if isinstance(opt, FusedAdam):
+        opt.gather_state()
+        exp_avg = opt.exp_avg
+    else:
+        exp_avg = opt.state[opt.param_groups[0]["params"][0]]["exp_avg"]
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    ps = model._ps
+    arrays = {"loss": loss.detach().float().reshape(1)}
+    for n in ps.names:
+        if ps.offsets[n] >= model.caption_param_end:
+            continue
+        k, o = ps.params[n].numel(), ps.offsets[n]
+        idx = None
+        if k > DUMP_SAMPLE:
+            rng = np.random.default_rng(zlib.crc32(n.encode()))
+            idx = torch.from_numpy(np.sort(rng.choice(k, DUMP_SAMPLE, replace=False))).to(exp_avg.device)
+        for prefix, flat in (("param", ps.flat), ("adam_exp_avg", exp_avg)):
+            v = flat[o:o + k]
+            arrays[f"{prefix}.{n}"] = v if idx is None else v[idx]
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v.detach().cpu().numpy().astype(np.float32))
 
 
 def cpu_baseline():
@@ -130,8 +169,7 @@ def exchange_path_n1(batch, dtype):
     out = {"what": "bench.py --force-exchange at world size 1 (own process per leg, 4 warm-up + 10 timed steps)"}
     for kind in ("sharded", "allreduce"):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "4", "--batch", str(batch),
-               "--dtype", dtype, "--force-exchange", "--exchange", kind, "--no-cpu-baseline", "--no-decode", "--no-b1024",
-               "--no-other-configs", "--no-exchange-line"]
+               "--dtype", dtype, "--force-exchange", "--exchange", kind]
         env = dict(os.environ, MASTER_PORT=str(29531 + (kind == "allreduce")))
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
@@ -238,6 +276,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: kernel brackets (roofline, north_star, hbm_kernels, comm timings), "
+                         "the batch-1024 side pass, other configs, decode, the exchange path at N=1 and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one produced (loss, parameters, Adam first moments; seeded samples of "
+                         "the large tensors) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--payload", default="bf16", choices=["fp32", "bf16"], help="gradient reduce-scatter / all-reduce payload (N > 1)")
     ap.add_argument("--exchange", default="sharded", choices=["sharded", "allreduce", "c10d"],
@@ -247,9 +291,9 @@ def main():
                     help="N=1: how the ~100 launches of a step are issued -- a C-side recorded launch list (default), Python/ctypes "
                          "eager launches, or a captured hipGraph")
     ap.add_argument("--graph", action="store_true", help="same as --executor graph")
-    ap.add_argument("--no-decode", action="store_true", help="skip the greedy-decode line (configs[4])")
-    ap.add_argument("--no-b1024", action="store_true", help="skip the north_star_b1024 side line (same kernels, per-GPU batch 1024)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the side lines of the shipped d=768 shape and configs[3] (d=1024, 6+6)")
+    ap.add_argument("--no-decode", action="store_true", help="--full: skip the greedy-decode line (configs[4])")
+    ap.add_argument("--no-b1024", action="store_true", help="--full: skip the north_star_b1024 side line (same kernels, per-GPU batch 1024)")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the side lines of the shipped d=768 shape and configs[3] (d=1024, 6+6)")
     ap.add_argument("--comm-cu-mask", type=int, default=0, help="N > 1: confine the communicator's stream (RCCL kernels) to the first N CUs")
     ap.add_argument("--overlap-adam", action="store_true", help="A/B: Adam per gradient bucket on the side stream during backward (measured slower)")
     ap.add_argument("--no-overlap-dw", action="store_true", help="A/B: weight-gradient GEMMs on the main stream")
@@ -257,7 +301,7 @@ def main():
     ap.add_argument("--no-overlap-enc", action="store_true", help="A/B: encoder backward after (not beside) the decoder's tail")
     ap.add_argument("--no-group-dw", action="store_true", help="A/B: one launch per weight-gradient GEMM instead of one per layer")
     ap.add_argument("--force-exchange", action="store_true", help="run the RCCL gradient exchange even at world size 1 (plumbing test)")
-    ap.add_argument("--no-exchange-line", action="store_true", help="skip the exchange_path_n1 side line (the N > 1 schedule at world size 1)")
+    ap.add_argument("--no-exchange-line", action="store_true", help="--full: skip the exchange_path_n1 side line (the N > 1 schedule at world size 1)")
     ap.add_argument("--torch-adam", action="store_true", help="A/B: torch.optim.Adam(fused=True) + cast kernels instead of vct_adam_step")
     args = ap.parse_args()
 
@@ -361,17 +405,17 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # live kernel timing: HIP events recorded by the C runtime on the launch stream, inside the timed region (they are part
-    # of the recorded launch list, so replays carry them too).  Every bracket is two event records in the stream and all of them
+    # --full only, live kernel timing: HIP events recorded by the C runtime on the launch stream, inside the timed region (they are
+    # part of the recorded launch list, so replays carry them too).  Every bracket is two event records in the stream and all of them
     # cost the step ~55 us (tools/taps_cost.py), so inside the timed region only ONE kernel is bracketed: the roofline kernel =
     # the LONGEST single launch of the step among the sample-stationary encoder / decoder stacks, the three generator GEMMs, the loss
     # and the optimizer's pass, chosen from the first half of the warm-up, which runs with those brackets on.  The other brackets
-    # (north_star, the rest of the top-5, ...) come from a short second pass.
+    # (north_star, the rest of the top-5, ...) come from a short second pass.  A plain run brackets nothing.
     GEN = ("gen_fwd", "gen_dx", "gen_dw")
     # candidates for the roofline kernel: every bracket that is ONE launch (or one launch + its fixed-order reduce) of the step
     CAND = GEN + ("ss_enc", "ss_dec", "loss", "adam")
     dom = "gen_dw"
-    w_probe = args.warmup // 2 if args.warmup >= 4 else 0
+    w_probe = args.warmup // 2 if args.full and args.warmup >= 4 else 0
     if w_probe:
         ops.taps_enable(True, only=CAND)
         for _ in range(w_probe):
@@ -382,51 +426,57 @@ def main():
         if probe:
             dom = max(probe, key=probe.get)
         trainer.drop_recordings()
-    ops.taps_enable(True, only=(dom,))
+    if args.full:
+        ops.taps_enable(True, only=(dom,))
     for _ in range(args.warmup - w_probe):
         loss = trainer.step(feats, mask, ids)
     sync()
-    for tag in ops.TAPS:
-        ops.tap_collect(tag)              # drop the warm-up brackets
+    if args.full:
+        for tag in ops.TAPS:
+            ops.tap_collect(tag)          # drop the warm-up brackets
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = trainer.step(feats, mask, ids)
     sync()
     elapsed = time.perf_counter() - t0
     final_loss = float(loss)          # of the last TIMED step (the loss buffer is static: the untimed passes below overwrite it)
-    taps = {tag: ops.tap_collect(tag) for tag in ops.TAPS}
-    # second pass, untimed: every bracket, fresh recordings (a recording contains the brackets that were active when it was made)
-    ops.taps_enable(True)
-    trainer.drop_recordings()
-    extra_steps = max(4, min(10, args.steps))
-    for _ in range(3):
-        trainer.step(feats, mask, ids)
-    sync()
-    for tag in ops.TAPS:
-        ops.tap_collect(tag)
-    for _ in range(extra_steps):
-        trainer.step(feats, mask, ids)
-    sync()
-    for tag in ops.TAPS:
-        if tag != dom:
-            taps[tag] = ops.tap_collect(tag)
-    # side line: the SAME kernels at a per-GPU batch of 1024 (what the 288 GB leave room for): how much of the north_star gap is
-    # the row count of configs[1] (M = 4864 / 3328 rows per GEMM) rather than the kernels
-    b1024 = None
-    if world == 1 and args.batch == 256 and not args.no_b1024:
-        ops.taps_enable(True, only=("layers_fwd", "step"))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, opt, loss, rank)
+    kern, extra_steps, b1024 = {}, 0, None
+    if args.full:
+        taps = {tag: ops.tap_collect(tag) for tag in ops.TAPS}
+        # second pass, untimed: every bracket, fresh recordings (a recording contains the brackets that were active when it was made)
+        ops.taps_enable(True)
         trainer.drop_recordings()
-        big = trainer.adopt_inputs(*synthetic(1024, rank, device))
+        extra_steps = max(4, min(10, args.steps))
         for _ in range(3):
-            trainer.step(*big)
+            trainer.step(feats, mask, ids)
         sync()
-        for tag in ("layers_fwd", "step"):
+        for tag in ops.TAPS:
             ops.tap_collect(tag)
-        for _ in range(6):
-            trainer.step(*big)
+        for _ in range(extra_steps):
+            trainer.step(feats, mask, ids)
         sync()
-        b1024 = {tag: float(np.mean(ops.tap_collect(tag))) for tag in ("layers_fwd", "step")}
-    ops.taps_enable(False)
+        for tag in ops.TAPS:
+            if tag != dom:
+                taps[tag] = ops.tap_collect(tag)
+        kern = {k: float(np.mean(v)) for k, v in taps.items() if v}   # ms per bracket, averaged over the timed steps
+        # side line: the SAME kernels at a per-GPU batch of 1024 (what the 288 GB leave room for): how much of the north_star gap is
+        # the row count of configs[1] (M = 4864 / 3328 rows per GEMM) rather than the kernels
+        if world == 1 and args.batch == 256 and not args.no_b1024:
+            ops.taps_enable(True, only=("layers_fwd", "step"))
+            trainer.drop_recordings()
+            big = trainer.adopt_inputs(*synthetic(1024, rank, device))
+            for _ in range(3):
+                trainer.step(*big)
+            sync()
+            for tag in ("layers_fwd", "step"):
+                ops.tap_collect(tag)
+            for _ in range(6):
+                trainer.step(*big)
+            sync()
+            b1024 = {tag: float(np.mean(ops.tap_collect(tag))) for tag in ("layers_fwd", "step")}
+        ops.taps_enable(False)
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -434,81 +484,8 @@ def main():
 
     if rank == 0:
         fl = algorithmic_flops(args.batch)
-        kern = {k: float(np.mean(v)) for k, v in taps.items() if v}   # ms per bracket, averaged over the timed steps
-        # roofline kernel = the LONGEST single launch of the step (picked above among CAND, bracketed inside the timed region).  The
-        # vocabulary weight gradient shares the chip with the encoder backward on the second stream, so its bracket is co-scheduled
-        # time -- that is what the step pays for it, and what is reported.
-        # HBM bytes per launch of the dominant kernel, from the committed PMC passes (profiles/): the entry must name the SAME
-        # kernel symbol the tag runs today -- a stale file (the kernel behind a tag changed) yields null, not a wrong number
-        fused_adam = bool(getattr(trainer, "fuse_adam", False))
-        Md, Vp = args.batch * (S_TOK - 1), (VOCAB + 31) // 32 * 32
-        esz = 2 if args.dtype == "bf16" else 4
-        n_par = model.caption_param_end
-        n_adam = getattr(opt, "range_elems", {}).get((0, model.encoder_param_begin), model.encoder_param_begin)
-        # tag -> (bound, algorithmic work per launch [FLOP | bytes], kernel symbol in a rocprofv3 kernel trace, description)
-        INFO = {
-            "gen_fwd": ("mfma", fl["gen"], "gemm256_kernel<0, 1, bf16>",
-                        "generator GEMM fwd 4864x30522x512 (gemm256_kernel NT: persistent 256x256 tiles, 8 waves, LDS-DMA double buffer)"),
-            "gen_dx": ("mfma", fl["gen"], "gemm256_kernel<0, 1, float>" if getattr(model.cap_decoder._engine(), "_wgt", None) is not None
-                       else "g32_kernel<0, 0, float",
-                       "generator dX GEMM 4864x512x30522 (g32_kernel NN: persistent 256x256 tiles, software-pipelined K loop on 32x32x16, "
-                       "split over K, + fixed-order reduce)"),
-            "gen_dw": ("mfma", fl["gen"], "g32_kernel<1, 0, float",
-                       "generator dW GEMM 30522x512x4864 (g32_kernel TN: persistent 256x256 tiles, software-pipelined K loop, transpose reads of "
-                       "both operands, bias gradient balanced over the waves, fp32 out" + (", torch.optim.Adam's step on W_g in its epilogue" if fused_adam else "")
-                       + "; runs beside the encoder backward)"),
-            "ss_enc": ("mfma", fl["enc_stack"], "layer_ss_fwd_kernel<false, 1>",
-                       "sample-stationary ENCODER stack forward, one launch: unify Linear + mean token + temporal encoding + 2 layers + final norm"),
-            "ss_dec": ("mfma", fl["dec_stack"], "layer_ss_fwd_kernel<true, 2>",
-                       "sample-stationary DECODER stack forward, one launch: token embedding + 2 layers (self-, cross-attention, feed-forward) + final norm"),
-            "loss": ("hbm", 2 * Md * Vp * esz, "sce_loss_kernel",
-                     "SCE loss + d/dlogits over the materialised logits: one read + one write"),
-            "adam": ("hbm", 30 * n_adam, "adam_ranges_kernel" if fused_adam else "adam_kernel",
-                     "optimizer pass over " + ("what the weight-gradient GEMMs' epilogues did not step (token embedding, biases, LayerNorm parameters)"
-                                                if fused_adam else "everything but the encoder") + ": 16 B read + 14 B written per parameter"),
-        }
         peak = PEAK_BF16_TFLOPS if args.dtype == "bf16" else PEAK_F32_TFLOPS
-
-        def roof(tag, ms_):
-            bound, work, _, _ = INFO[tag]
-            if bound == "mfma":
-                ach, pk, unit = work / (ms_ * 1e-3) / 1e12, peak, "TFLOP/s"
-            else:
-                ach, pk, unit = work / (ms_ * 1e-3) / 1e9, PEAK_HBM_GBS, "GB/s"
-            return bound, ach, pk, unit
-        traffic, traffic_src = None, None
-        for name in ("r06_roofline_traffic.json", "r05_roofline_traffic.json", "r04_roofline_traffic.json"):
-            try:
-                tj = json.load(open(os.path.join(ROOT, "profiles", name)))
-                ent = tj[dom]
-                if args.batch == 256 and args.dtype == "bf16" and INFO[dom][2] in str(ent.get("kernel", "")):
-                    traffic, traffic_src = ent["hbm_bytes"], f"rocprofv3 PMC FETCH_SIZE x2 + WRITE_SIZE of {INFO[dom][2]}, profiles/{name}"
-                    break
-            except Exception:
-                continue
-        r_bound, achieved, r_peak, r_unit = roof(dom, kern[dom])
         ms = elapsed / args.steps * 1e3
-        top5 = sorted(((k, kern[k]) for k in CAND if k in kern), key=lambda kv: -kv[1])[:5]
-        hbm = {}
-        if "loss" in kern:      # SCE loss + d/dlogits: one read + one write of the logits
-            by = 2 * Md * Vp * esz
-            hbm["sce_loss"] = {"bytes": by, "ms": round(kern["loss"], 4), "achieved": round(by / (kern["loss"] * 1e-3) / 1e9, 1),
-                               "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(by / (kern["loss"] * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)}
-        if "adam" in kern:      # Adam over everything but the encoder: 16 B read + 12 B written (+2 B shadow) per parameter
-            by = 30 * n_adam
-            hbm["adam"] = {"bytes": by, "ms": round(kern["adam"], 4), "achieved": round(by / (kern["adam"] * 1e-3) / 1e9, 1),
-                           "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(by / (kern["adam"] * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
-                           "note": f"{n_adam} of {n_par} parameters in this launch" + (" (weight matrices are stepped inside their weight-gradient GEMMs)"
-                                                                                         if fused_adam else " (the encoder's follow in a second launch)")}
-        north = None
-        if "layers_fwd" in kern:
-            lf = kern["layers_fwd"]
-            north = {"what": "attention + FFN forward of the 2 encoder + 2 decoder layers (north_star target: >= 40 % of bf16 MFMA peak); "
-                             "bracket = main-stream HIP events from the input cast to the decoder's final LayerNorm, i.e. it also "
-                             "contains the unify GEMM, the encoder front end and the token embedding (not counted as FLOPs)",
-                     "flops": fl["attn_ffn_fwd"], "ms": round(lf, 4), "tflops": round(fl["attn_ffn_fwd"] / (lf * 1e-3) / 1e12, 1),
-                     "frac_of_peak": round(fl["attn_ffn_fwd"] / (lf * 1e-3) / 1e12 / peak, 4), "target_frac": 0.40,
-                     "two_stream_overlap": not args.no_overlap_enc}
         out = {
             "metric": "video-caption train samples/sec (whole node)",
             "value": round(args.batch * world * args.steps / elapsed, 1), "unit": "samples/s",
@@ -521,26 +498,103 @@ def main():
                        "executor": "eager" if not (trainer.use_list or trainer.use_graph) else ("list" if trainer.use_list else "graph")},
             "step_tflops": round(fl["step"] / (ms * 1e-3) / 1e12, 1),
             "step_frac_of_peak": round(fl["step"] / (ms * 1e-3) / 1e12 / peak, 4),
-            "roofline": {"bound": r_bound, "kernel_tag": dom, "kernel": INFO[dom][3], "kernel_symbol": INFO[dom][2],
-                         "selection": "longest single launch of the step among " + " / ".join(CAND) + " in the warm-up probe",
-                         "achieved": round(achieved, 1), "peak": r_peak, "unit": r_unit, "frac": round(achieved / r_peak, 4),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         ("flops_per_launch" if r_bound == "mfma" else "bytes_per_launch"): INFO[dom][1], "avg_ms_per_launch": round(kern[dom], 4),
-                         "top5": [{"kernel_tag": k, "kernel": INFO[k][2], "bound": roof(k, v)[0], "ms": round(v, 4),
-                                   "frac": round(roof(k, v)[1] / roof(k, v)[2], 4)} for k, v in top5],
-                         "generator_gemms": {k: {"ms": round(kern[k], 4), "tflops": round(fl["gen"] / (kern[k] * 1e-3) / 1e12, 1),
-                                                 "frac": round(fl["gen"] / (kern[k] * 1e-3) / 1e12 / peak, 4)} for k in GEN if k in kern},
-                         "all_ms": {k: round(v, 4) for k, v in kern.items()},
-                         "all_ms_source": f"{dom}: HIP events inside the timed region; the other brackets: a second, untimed pass "
-                                          f"of {extra_steps} steps with every bracket on (all seven cost the step ~55 us)"},
-            "north_star": north,
-            "north_star_b1024": None if b1024 is None else {
-                "what": "the same kernels and schedule at a per-GPU batch of 1024 (untimed side pass, 6 steps): attention + FFN forward",
-                "flops": algorithmic_flops(1024)["attn_ffn_fwd"], "ms": round(b1024["layers_fwd"], 4),
-                "tflops": round(algorithmic_flops(1024)["attn_ffn_fwd"] / (b1024["layers_fwd"] * 1e-3) / 1e12, 1),
-                "frac_of_peak": round(algorithmic_flops(1024)["attn_ffn_fwd"] / (b1024["layers_fwd"] * 1e-3) / 1e12 / peak, 4),
-                "step_ms": round(b1024["step"], 4), "samples_per_s": round(1024 / (b1024["step"] * 1e-3), 1)},
-            "hbm_kernels": hbm,
+        }
+        if args.full:
+            # roofline kernel = the LONGEST single launch of the step (picked above among CAND, bracketed inside the timed region).  The
+            # vocabulary weight gradient shares the chip with the encoder backward on the second stream, so its bracket is co-scheduled
+            # time -- that is what the step pays for it, and what is reported.
+            # HBM bytes per launch of the dominant kernel, from the committed PMC passes (profiles/): the entry must name the SAME
+            # kernel symbol the tag runs today -- a stale file (the kernel behind a tag changed) yields null, not a wrong number
+            fused_adam = bool(getattr(trainer, "fuse_adam", False))
+            Md, Vp = args.batch * (S_TOK - 1), (VOCAB + 31) // 32 * 32
+            esz = 2 if args.dtype == "bf16" else 4
+            n_par = model.caption_param_end
+            n_adam = getattr(opt, "range_elems", {}).get((0, model.encoder_param_begin), model.encoder_param_begin)
+            # tag -> (bound, algorithmic work per launch [FLOP | bytes], kernel symbol in a rocprofv3 kernel trace, description)
+            INFO = {
+                "gen_fwd": ("mfma", fl["gen"], "gemm256_kernel<0, 1, bf16>",
+                            "generator GEMM fwd 4864x30522x512 (gemm256_kernel NT: persistent 256x256 tiles, 8 waves, LDS-DMA double buffer)"),
+                "gen_dx": ("mfma", fl["gen"], "gemm256_kernel<0, 1, float>" if getattr(model.cap_decoder._engine(), "_wgt", None) is not None
+                           else "g32_kernel<0, 0, float",
+                           "generator dX GEMM 4864x512x30522 (g32_kernel NN: persistent 256x256 tiles, software-pipelined K loop on 32x32x16, "
+                           "split over K, + fixed-order reduce)"),
+                "gen_dw": ("mfma", fl["gen"], "g32_kernel<1, 0, float",
+                           "generator dW GEMM 30522x512x4864 (g32_kernel TN: persistent 256x256 tiles, software-pipelined K loop, transpose reads of "
+                           "both operands, bias gradient balanced over the waves, fp32 out" + (", torch.optim.Adam's step on W_g in its epilogue" if fused_adam else "")
+                           + "; runs beside the encoder backward)"),
+                "ss_enc": ("mfma", fl["enc_stack"], "layer_ss_fwd_kernel<false, 1>",
+                           "sample-stationary ENCODER stack forward, one launch: unify Linear + mean token + temporal encoding + 2 layers + final norm"),
+                "ss_dec": ("mfma", fl["dec_stack"], "layer_ss_fwd_kernel<true, 2>",
+                           "sample-stationary DECODER stack forward, one launch: token embedding + 2 layers (self-, cross-attention, feed-forward) + final norm"),
+                "loss": ("hbm", 2 * Md * Vp * esz, "sce_loss_kernel",
+                         "SCE loss + d/dlogits over the materialised logits: one read + one write"),
+                "adam": ("hbm", 30 * n_adam, "adam_ranges_kernel" if fused_adam else "adam_kernel",
+                         "optimizer pass over " + ("what the weight-gradient GEMMs' epilogues did not step (token embedding, biases, LayerNorm parameters)"
+                                                    if fused_adam else "everything but the encoder") + ": 16 B read + 14 B written per parameter"),
+            }
+
+            def roof(tag, ms_):
+                bound, work, _, _ = INFO[tag]
+                if bound == "mfma":
+                    ach, pk, unit = work / (ms_ * 1e-3) / 1e12, peak, "TFLOP/s"
+                else:
+                    ach, pk, unit = work / (ms_ * 1e-3) / 1e9, PEAK_HBM_GBS, "GB/s"
+                return bound, ach, pk, unit
+            traffic, traffic_src = None, None
+            for name in ("r06_roofline_traffic.json", "r05_roofline_traffic.json", "r04_roofline_traffic.json"):
+                try:
+                    tj = json.load(open(os.path.join(ROOT, "profiles", name)))
+                    ent = tj[dom]
+                    if args.batch == 256 and args.dtype == "bf16" and INFO[dom][2] in str(ent.get("kernel", "")):
+                        traffic, traffic_src = ent["hbm_bytes"], f"rocprofv3 PMC FETCH_SIZE x2 + WRITE_SIZE of {INFO[dom][2]}, profiles/{name}"
+                        break
+                except Exception:
+                    continue
+            r_bound, achieved, r_peak, r_unit = roof(dom, kern[dom])
+            top5 = sorted(((k, kern[k]) for k in CAND if k in kern), key=lambda kv: -kv[1])[:5]
+            hbm = {}
+            if "loss" in kern:      # SCE loss + d/dlogits: one read + one write of the logits
+                by = 2 * Md * Vp * esz
+                hbm["sce_loss"] = {"bytes": by, "ms": round(kern["loss"], 4), "achieved": round(by / (kern["loss"] * 1e-3) / 1e9, 1),
+                                   "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(by / (kern["loss"] * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)}
+            if "adam" in kern:      # Adam over everything but the encoder: 16 B read + 12 B written (+2 B shadow) per parameter
+                by = 30 * n_adam
+                hbm["adam"] = {"bytes": by, "ms": round(kern["adam"], 4), "achieved": round(by / (kern["adam"] * 1e-3) / 1e9, 1),
+                               "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(by / (kern["adam"] * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
+                               "note": f"{n_adam} of {n_par} parameters in this launch" + (" (weight matrices are stepped inside their weight-gradient GEMMs)"
+                                                                                             if fused_adam else " (the encoder's follow in a second launch)")}
+            north = None
+            if "layers_fwd" in kern:
+                lf = kern["layers_fwd"]
+                north = {"what": "attention + FFN forward of the 2 encoder + 2 decoder layers (north_star target: >= 40 % of bf16 MFMA peak); "
+                                 "bracket = main-stream HIP events from the input cast to the decoder's final LayerNorm, i.e. it also "
+                                 "contains the unify GEMM, the encoder front end and the token embedding (not counted as FLOPs)",
+                         "flops": fl["attn_ffn_fwd"], "ms": round(lf, 4), "tflops": round(fl["attn_ffn_fwd"] / (lf * 1e-3) / 1e12, 1),
+                         "frac_of_peak": round(fl["attn_ffn_fwd"] / (lf * 1e-3) / 1e12 / peak, 4), "target_frac": 0.40,
+                         "two_stream_overlap": not args.no_overlap_enc}
+            out.update({
+                "roofline": {"bound": r_bound, "kernel_tag": dom, "kernel": INFO[dom][3], "kernel_symbol": INFO[dom][2],
+                             "selection": "longest single launch of the step among " + " / ".join(CAND) + " in the warm-up probe",
+                             "achieved": round(achieved, 1), "peak": r_peak, "unit": r_unit, "frac": round(achieved / r_peak, 4),
+                             "traffic": traffic, "traffic_source": traffic_src,
+                             ("flops_per_launch" if r_bound == "mfma" else "bytes_per_launch"): INFO[dom][1], "avg_ms_per_launch": round(kern[dom], 4),
+                             "top5": [{"kernel_tag": k, "kernel": INFO[k][2], "bound": roof(k, v)[0], "ms": round(v, 4),
+                                       "frac": round(roof(k, v)[1] / roof(k, v)[2], 4)} for k, v in top5],
+                             "generator_gemms": {k: {"ms": round(kern[k], 4), "tflops": round(fl["gen"] / (kern[k] * 1e-3) / 1e12, 1),
+                                                     "frac": round(fl["gen"] / (kern[k] * 1e-3) / 1e12 / peak, 4)} for k in GEN if k in kern},
+                             "all_ms": {k: round(v, 4) for k, v in kern.items()},
+                             "all_ms_source": f"{dom}: HIP events inside the timed region; the other brackets: a second, untimed pass "
+                                              f"of {extra_steps} steps with every bracket on (all seven cost the step ~55 us)"},
+                "north_star": north,
+                "north_star_b1024": None if b1024 is None else {
+                    "what": "the same kernels and schedule at a per-GPU batch of 1024 (untimed side pass, 6 steps): attention + FFN forward",
+                    "flops": algorithmic_flops(1024)["attn_ffn_fwd"], "ms": round(b1024["layers_fwd"], 4),
+                    "tflops": round(algorithmic_flops(1024)["attn_ffn_fwd"] / (b1024["layers_fwd"] * 1e-3) / 1e12, 1),
+                    "frac_of_peak": round(algorithmic_flops(1024)["attn_ffn_fwd"] / (b1024["layers_fwd"] * 1e-3) / 1e12 / peak, 4),
+                    "step_ms": round(b1024["step"], 4), "samples_per_s": round(1024 / (b1024["step"] * 1e-3), 1)},
+                "hbm_kernels": hbm,
+            })
+        out.update({
             "loss": final_loss,
             # data-parallel exchange evidence (null at N = 1): ranks of the RCCL communicator, what the compute stream waits for it at
             # the end of a step, and how long each gradient bucket occupies the communicator's stream (second, untimed pass)
@@ -550,15 +604,16 @@ def main():
                 "bucket_ms_on_comm_stream": [round(kern[f"comm_b{i}"], 4) if f"comm_b{i}" in kern else None
                                              for i in range(min(8, len(model.grad_buckets())))],
                 "buckets": "generator | decoder layers top-down | token embedding | encoder layers top-down (+ unify)"},
-        }
-        if world == 1 and args.batch == 256 and not args.no_other_configs:
-            out["other_configs"] = other_configs(device, model.compute_dtype, peak)
-        if world == 1 and not args.no_decode:
-            out["decode"] = decode_line(device, model.compute_dtype)
-        if world == 1 and not args.no_exchange_line and not args.force_exchange and args.batch == 256:
-            out["exchange_path_n1"] = exchange_path_n1(args.batch, args.dtype)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline()
+        })
+        if args.full:
+            if world == 1 and args.batch == 256 and not args.no_other_configs:
+                out["other_configs"] = other_configs(device, model.compute_dtype, peak)
+            if world == 1 and not args.no_decode:
+                out["decode"] = decode_line(device, model.compute_dtype)
+            if world == 1 and not args.no_exchange_line and not args.force_exchange and args.batch == 256:
+                out["exchange_path_n1"] = exchange_path_n1(args.batch, args.dtype)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline()
         json_out.write(json.dumps(out) + "\n")
         json_out.flush()
     if dist.is_initialized():

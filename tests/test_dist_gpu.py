@@ -202,10 +202,11 @@ def test_four_ranks_one_gpu_sharded_recorded_step(dtype_name):
     _run_ranks(4, dtype_name, True, "list")
 
 
-def test_bench_two_rank_control_flow_on_one_gpu():
-    """bench.py --gpus 2 as the driver launches it (one process per rank, RANK / WORLD_SIZE / MASTER_* from the env), with both
-    ranks on the ONE GPU of the test box and gloo as the process group: barrier, MAX-reduce of the elapsed time, rank-0-only
-    JSON line, whole-job value = 2 x per-GPU batch x steps / time, sharded exchange through the torch.distributed collectives."""
+def test_bench_two_rank_control_flow_on_one_gpu(tmp_path):
+    """bench.py --gpus 2 --full as the driver launches it (one process per rank, RANK / WORLD_SIZE / MASTER_* from the env), with
+    both ranks on the ONE GPU of the test box and gloo as the process group: barrier, MAX-reduce of the elapsed time, rank-0-only
+    JSON line, whole-job value = 2 x per-GPU batch x steps / time, sharded exchange through the torch.distributed collectives,
+    the exchange's brackets (--full), and --dump-outputs after the moments were gathered from both ranks."""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     import json
@@ -218,7 +219,8 @@ def test_bench_two_rank_control_flow_on_one_gpu():
         env = dict(os.environ, RANK=str(r), WORLD_SIZE="2", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                    VCT_DIST_BACKEND="gloo")
         procs.append(subprocess.Popen([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-                                       "--batch", "16", "--no-cpu-baseline", "--no-decode"], env=env, cwd=root,
+                                       "--batch", "16", "--full", "--no-cpu-baseline", "--no-decode", "--dump-outputs", str(tmp_path)],
+                                      env=env, cwd=root,
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=600) for p in procs]
     assert all(p.returncode == 0 for p in procs), [o[1][-2000:] for o in outs]
@@ -235,3 +237,10 @@ def test_bench_two_rank_control_flow_on_one_gpu():
     c = d["comm"]
     assert c["kind"].startswith("sharded/") and "rccl_ranks" in c and c["exposed_wait_ms"] is not None
     assert len(c["bucket_ms_on_comm_stream"]) >= 4 and all(v is not None and v > 0 for v in c["bucket_ms_on_comm_stream"])
+    import numpy as np
+    loss = np.load(tmp_path / "loss.npy")
+    assert loss.dtype == np.float32 and loss.tolist() == [d["loss"]]
+    m = np.load(tmp_path / "adam_exp_avg.cap_decoder.generator.weight.npy")
+    e = np.load(tmp_path / "adam_exp_avg.video_encoder.transformer_encoder.layers.0.linear1.weight.npy")
+    # rank 1 steps its half of every bucket's moments: without the gather rank 0 would write zeros there
+    assert m.dtype == np.float32 and np.isfinite(m).all() and (m != 0).mean() > 0.9 and (e != 0).mean() > 0.9

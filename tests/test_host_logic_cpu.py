@@ -160,3 +160,42 @@ def test_optimizer_ranges_left_by_the_weight_gradient_epilogues():
         want_blk.append(at); at += (b - a + 4095) // 4096
     assert [r.blk0 for r in arr] == want_blk and blocks == at
     assert [(r.begin, r.end, r.shadow) for r in arr] == [(a, b, int(sh)) for a, b, sh in left]
+
+
+def test_bench_output_dump_is_seeded_and_bounded(tmp_path):
+    """bench.py --dump-outputs: the loss and, per caption-path parameter, the fp32 master and Adam's first moment as float32 .npy
+    files; a tensor above bench.DUMP_SAMPLE elements as the elements at positions drawn from a generator seeded by its name (the
+    same positions on every run and every build), at most 64 MB in all at the benchmark's own configuration."""
+    import zlib
+    import bench
+    from vct_amd.model import MMT4Caption
+    from vct_amd.trainer import build_optimizer
+    torch.manual_seed(0)
+    m = MMT4Caption(bench.MODEL_CFG, device=torch.device("cpu"), compute_dtype=torch.float32)
+    m.mode("caption")
+    opt, _ = build_optimizer(bench.TRAIN_CFG, m)
+    m.flat_grads.copy_(torch.randn(m.flat_grads.shape))
+    opt.step()
+    exp_avg = opt.state[opt.param_groups[0]["params"][0]]["exp_avg"]
+    loss = torch.tensor([9.5])
+    bench.dump_outputs(str(tmp_path / "a"), m, opt, loss, rank=0)
+    bench.dump_outputs(str(tmp_path / "b"), m, opt, loss, rank=0)
+    bench.dump_outputs(str(tmp_path / "c"), m, opt, loss, rank=1)          # other ranks write nothing
+    assert not (tmp_path / "c").exists()
+    ps = m._ps
+    names = ["loss"] + [f"{p}.{n}" for n in ps.names for p in ("param", "adam_exp_avg")]
+    assert sorted(f.name for f in (tmp_path / "a").iterdir()) == sorted(n + ".npy" for n in names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20, total
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [9.5]
+    for n in ("cap_decoder.generator.weight", "cap_decoder.generator.bias"):
+        k, o = ps.params[n].numel(), ps.offsets[n]
+        idx = np.arange(k)
+        if k > bench.DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(zlib.crc32(n.encode())).choice(k, bench.DUMP_SAMPLE, replace=False))
+        assert np.array_equal(np.load(tmp_path / "a" / f"param.{n}.npy"), ps.flat[o:o + k].numpy()[idx])
+        assert np.array_equal(np.load(tmp_path / "a" / f"adam_exp_avg.{n}.npy"), exp_avg[o:o + k].numpy()[idx])

@@ -5,10 +5,10 @@ set -u
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$1; TAG=$2; mkdir -p $OUT
 cd $R
-python bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+python bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_list
-rocprofv3 --kernel-trace --stats -d /tmp/prof_list -o r -- python $R/bench.py --no-cpu-baseline --no-decode --no-b1024 --no-other-configs --no-exchange-line > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err
+rocprofv3 --kernel-trace --stats -d /tmp/prof_list -o r -- python $R/bench.py --full --no-cpu-baseline --no-decode --no-b1024 --no-other-configs --no-exchange-line > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err
 cd $R
 db=$(find /tmp/prof_list -name "*results.db" | head -1)
 python tools/rocpd_summary.py $db --skip-frac 0.35 > $OUT/bench_list_kernel_summary.txt 2>&1
