@@ -405,6 +405,27 @@ int vct_greedy_select(int dtype, int rows, int cols, const void* x, int64_t ldx,
                       int64_t end_id, uint8_t* ended, int32_t* ended_count, int64_t* all_ended_at, int32_t t,
                       void* stream);
 /* ---------------------------------------------------------------------------------------------
+ * Beam search on the KV-cached decode step (csrc/vct_beam.hip).
+ * replaces: MMT4Caption.beam_decode (MMT4Caption.py:186, `pass` in the reference) and predict_video.py:170's `--beam N`
+ * ("not support yet").  Semantics: decode.beam_decode_ids (fixed-width beams, finished hypotheses frozen).
+ *
+ * vct_beam_select: one selection step for B videos of K beams (1 <= K <= 16, K <= V; rows b*K .. b*K+K-1 of x are video b).
+ *   x [B*K, ldx] bf16 / fp32 logits (V valid columns, ldx >= V); scores fp32 [B*K] and finished uint8 [B*K] are read and
+ *   rewritten in place; parent int32 [B*K] receives the parent ROW (b*K + k) of every new slot; out[row * out_stride] (int64,
+ *   column t of the token table) the appended token (pad_id for a finished parent).  finished_count: this step's int32
+ *   counter (zero before the call); the call whose videos complete the set of B*K finished slots stores t into
+ *   all_finished_at[0] (atomic min).  Two launches.  workspace: >= B*K*CH*(2 + 2K)*4 bytes, CH = ceil(V / (256 * (16 /
+ *   sizeof(dtype))))  (else VCT_E_WORKSPACE).
+ * vct_beam_reorder: for every layer l < L, row j < M and slot s < t: dst[l][j*Lmax + s][d:3d] = src[l][parent[j]*Lmax + s][d:3d]
+ *   (cache rows of 3d elements, layer l at element offset l * layer_stride; src != dst: the other cache of a ping-pong pair).
+ *   One launch. */
+int vct_beam_select(int dtype, int B, int K, int V, const void* x, int64_t ldx, float* scores, uint8_t* finished,
+                    int32_t* parent, int64_t* out, int64_t out_stride, int64_t end_id, int64_t pad_id,
+                    int32_t* finished_count, int64_t* all_finished_at, int32_t t, void* workspace, int64_t workspace_bytes,
+                    void* stream);
+int vct_beam_reorder(int dtype, int L, int M, int Lmax, int d, int t, const int32_t* parent, const void* src, void* dst,
+                     int64_t layer_stride, void* stream);
+/* ---------------------------------------------------------------------------------------------
  * One stage of the greedy-decode step at SMALL batch (B <= 4): out[b, n] = epilogue(W[n, :] . prologue(...)[b, :]), a weight-
  * streaming matrix-vector kernel whose prologue builds the input vector and whose epilogue finishes the stage, so that the
  * embedding / LayerNorm / attention launches of the per-token step vanish into their consumers (csrc/vct_decode.hip):

@@ -9,11 +9,14 @@ Two implementations with identical results (tests/test_model_gpu.py):
     in a hipGraph per position and replayed; end-of-sequence bookkeeping stays on the device and the
     host reads it `lookahead` steps behind the launch front, so the device never idles on the check.
     The reference's stop rule (stop when EVERY row has emitted [SEP] at least once) is honoured by
-    truncating the id matrix at that step."""
+    truncating the id matrix at that step.
+
+Beam search (`beam_decode_ids`, `beam_decode_ids_reference_algorithm`): the reference has none (MMT4Caption.py:186 is a stub,
+predict_video.py:170's `--beam` says "not support yet"); the semantics are stated in `beam_decode_ids`."""
 import torch
 
 from . import ops
-from .engine import DecodeState
+from .engine import BeamDecodeState, DecodeState
 from .utils import capture_graph
 
 
@@ -59,12 +62,20 @@ def greedy_decode_ids(model, feats: torch.Tensor, mask, max_len: int = 30, use_g
     steps, reads the device-side "every caption has ended at step s" word as of the step that left the queue (a copy on a second
     stream issued once the host has seen THAT step's event complete) -- the reference syncs on every token (`.tolist()`, MMT4Caption.py:168).  A
     caption batch that ends at step s therefore costs at most s + lookahead steps; the id matrix is truncated at s."""
+    dec = model.cap_decoder._engine()
+    B, T = feats.shape[0], feats.shape[1]
+    st = _session(model, dec, B, T + 1, max_len)
+    stop = _run_session(model, st, feats, mask, max_len, use_graphs, sync_every, lookahead, dec.decode_begin, dec.decode_step)
+    return st.ys[:, :stop + 1].clone()
+
+
+def _run_session(model, st, feats, mask, max_len, use_graphs, sync_every, lookahead, begin, step) -> int:
+    """The token loop shared by greedy and beam decoding: prologue (encoder + begin), one captured graph per position, the
+    device-side stop word polled `lookahead` steps behind the launch front.  Returns the last step to keep."""
     pre = model.cap_preprocessor
     model._ps.refresh_shadow()
     model._ps.refresh_lazy_transposed()
-    enc, dec = model.video_encoder._engine(), model.cap_decoder._engine()
-    B, T = feats.shape[0], feats.shape[1]
-    st = _session(model, dec, B, T + 1, max_len)
+    enc = model.video_encoder._engine()
     stamp = model._ps._stamp
     if st.__dict__.get("weights_stamp") != stamp:      # graphs bake weight pointers only, but keep it simple and safe
         st.weights_stamp = stamp
@@ -85,10 +96,10 @@ def greedy_decode_ids(model, feats: torch.Tensor, mask, max_len: int = 30, use_g
             fin.copy_(feats)
             if mask is not None:
                 min_.copy_(mask)
-            dec.decode_begin(st, enc.forward(fin, min_, False), pre.start_id, pre.pad_id)      # warm-up: allocates
+            begin(st, enc.forward(fin, min_, False), pre.start_id, pre.pad_id)      # warm-up: allocates
             g = torch.cuda.CUDAGraph()
             with capture_graph(g):
-                dec.decode_begin(st, enc.forward(fin, min_, False), pre.start_id, pre.pad_id)
+                begin(st, enc.forward(fin, min_, False), pre.start_id, pre.pad_id)
             st.begin = {"key": key, "gen": model._ps.ctx.generation, "g": g, "fin": fin, "min": min_}
         else:
             bg["fin"].copy_(feats)
@@ -96,7 +107,7 @@ def greedy_decode_ids(model, feats: torch.Tensor, mask, max_len: int = 30, use_g
                 bg["min"].copy_(mask)
             bg["g"].replay()
     else:
-        dec.decode_begin(st, enc.forward(feats, mask, False), pre.start_id, pre.pad_id)
+        begin(st, enc.forward(feats, mask, False), pre.start_id, pre.pad_id)
     stop = max_len
 
     def ended_as_of(step: int) -> int:
@@ -114,16 +125,16 @@ def greedy_decode_ids(model, feats: torch.Tensor, mask, max_len: int = 30, use_g
         if use_graphs:
             g = st.graphs.get(t)
             if g is None:
-                dec.decode_step(st, t, pre.end_id)         # warm-up run (allocates the step's temporaries)
+                step(st, t, pre.end_id)         # warm-up run (allocates the step's temporaries)
                 # the warm-up already wrote ys[:, t]; capture replays the same work
                 g = torch.cuda.CUDAGraph()
                 with capture_graph(g):
-                    dec.decode_step(st, t, pre.end_id)
+                    step(st, t, pre.end_id)
                 st.graphs[t] = g
             else:
                 g.replay()
         else:
-            dec.decode_step(st, t, pre.end_id)
+            step(st, t, pre.end_id)
         if not on_gpu:
             continue
         if t % sync_every == 0 or t == max_len - 1:
@@ -138,7 +149,7 @@ def greedy_decode_ids(model, feats: torch.Tensor, mask, max_len: int = 30, use_g
     else:
         if on_gpu:
             stop = min(stop, ended_as_of(max_len - 1))
-    return st.ys[:, :min(stop, max_len - 1) + 1].clone()
+    return min(stop, max_len - 1)
 
 
 @torch.no_grad()
@@ -165,3 +176,137 @@ def teacher_forced_next_ids(model, feats: torch.Tensor, mask, prefix_ids: torch.
         if return_logits:
             logits[:, t - 1] = st.last_logits[:, :dec.V].float()
     return (out, logits) if return_logits else out
+
+
+def _beam_session(model, dec, B, K, Te, max_len) -> BeamDecodeState:
+    cache = model.__dict__.setdefault("_decode_sessions", {})
+    key = ("beam", B, K, Te, max_len, dec.dt)          # never a greedy session's key
+    st = cache.get(key)
+    if st is None:
+        if len(cache) > 3:
+            cache.clear()
+        st = cache[key] = BeamDecodeState(dec, B, K, Te, max_len)
+    return st
+
+
+def _beam_finish(ids: torch.Tensor, scores: torch.Tensor, B: int, K: int, end_id: int, length_penalty: float, return_all: bool):
+    """ids [B*K, L'] (slot order), raw scores fp32 [B*K] -> the slots of each video sorted by s / n^alpha (descending, ties to
+    the lower slot), n = generated tokens up to and including the first end_id (all of them if none)."""
+    gen = ids[:, 1:] == end_id
+    n_all = ids.shape[1] - 1
+    first = torch.where(gen.any(1), gen.int().argmax(1) + 1, torch.full_like(gen[:, 0], n_all, dtype=torch.long))
+    final = scores.float() / first.float().pow(float(length_penalty))
+    final = final.view(B, K)
+    final, order = torch.sort(final, dim=1, descending=True, stable=True)
+    ids = ids.view(B, K, -1).gather(1, order[:, :, None].expand(-1, -1, ids.shape[1]))
+    if return_all:
+        return ids, final
+    return ids[:, 0].contiguous()
+
+
+@torch.no_grad()
+def beam_decode_ids(model, feats: torch.Tensor, mask, beam_size: int, max_len: int = 30, length_penalty: float = 1.0,
+                    use_graphs: bool = True, return_all: bool = False, sync_every: int = 4, lookahead: int = 3):
+    """Beam search on the KV-cached decode step.  Returns the best ids int64 [B, L'] (L' <= max_len), or with return_all
+    (ids [B, K, L'], final scores fp32 [B, K]), each video's beams sorted best first.
+
+    Semantics (fixed-width beams, finished hypotheses frozen -- NOT a separate finished pool as in Hugging Face's generate):
+    K = beam_size (1 <= K <= 16, K <= V) slots per video, each a token history, a cumulative fp32 score s and a finished flag.
+    Start: every slot is [start_id], unfinished, s = 0 for slot 0 and -inf for the others.  Step t = 1 .. max_len-1:
+    logp[k, v] = logit[k, v] - logsumexp(logit[k, :V]) in fp32 (logits as the decode step produces them: bf16 on the bf16
+    paths); an unfinished slot offers the V candidates (k, v) valued s[k] + logp[k, v], a finished slot the one candidate
+    (k, pad_id) valued s[k]; the K highest values (ties: smaller flat index k*V + v) become the new slots in rank order,
+    each its parent's history + v, score = the value, finished = parent finished or v == end_id.  Stop at the first step
+    after which every slot of every video is finished, or at max_len-1 (greedy's stop rule on beams; the id matrix is cut
+    there).  Final score s / n^length_penalty, n = generated tokens up to and including the first end_id (all of them for a
+    slot that never finished); slots sorted by it, descending, ties to the lower slot.  Layout as greedy's:
+    [start, tokens, end, pad...] (a finished beam appends pad_id where greedy appends arg-max tokens).
+
+    K = 1 gives greedy_decode_ids' ids up to and including each row's first end_id, and the same length -- except where an fp32
+    rounding coincidence turns two distinct logits into equal logp (the kernel ranks a row's candidates by logit).
+
+    One captured hipGraph per position (it bakes the ping-pong side of the cache), the begin graph and the stop polling of
+    greedy_decode_ids.  The batch-1 block step is greedy-only: beams run on the gemv (B*K = 1), fused (bf16, 2..256 rows) or
+    generic batched step."""
+    pre = model.cap_preprocessor
+    dec = model.cap_decoder._engine()
+    K = int(beam_size)
+    if not 1 <= K <= 16 or K > dec.V:
+        raise ValueError(f"beam_size must be in 1..16 and <= the vocabulary size, got {beam_size}")
+    B, T = feats.shape[0], feats.shape[1]
+    st = _beam_session(model, dec, B, K, T + 1, max_len)
+    stop = _run_session(model, st, feats, mask, max_len, use_graphs, sync_every, lookahead, dec.beam_begin, dec.beam_step)
+    # back-track the parent rows once: column t of slot j is the token appended at step t by the slot's ancestor
+    M = B * K
+    ids = torch.empty(M, stop + 1, dtype=torch.long, device=feats.device)
+    ids[:, 0] = pre.start_id
+    r = torch.arange(M, device=feats.device)
+    for t in range(stop, 0, -1):
+        ids[:, t] = st.ys[r, t]
+        r = st.parents[t].long()[r]
+    # steps that ran past `stop` (lookahead) saw only finished slots, already in rank order: they left the scores as they were
+    return _beam_finish(ids, st.scores.clone(), B, K, pre.end_id, length_penalty, return_all)
+
+
+def _select_ref(vals: torch.Tensor, valid: torch.Tensor, K: int):
+    """Host-side selection of one step for every video: vals / valid [B, K*V] -> (flat indices [B, K], values [B, K], margin
+    between the K-th and (K+1)-th candidate, inf where there is no (K+1)-th).  Stable sorts: value descending, flat index
+    ascending on ties, invalid entries last."""
+    v = torch.where(valid, vals, torch.full_like(vals, float("-inf")))
+    order = torch.sort(v, dim=1, descending=True, stable=True)[1]
+    order = order.gather(1, torch.sort(valid.gather(1, order).int(), dim=1, descending=True, stable=True)[1])
+    top = order[:, :K + 1]
+    tv = v.gather(1, top)
+    ok = valid.gather(1, top)
+    margin = float("inf")
+    if top.shape[1] > K:
+        gap = (tv[:, K - 1].double() - tv[:, K].double())[ok[:, K] & torch.isfinite(tv[:, K])]
+        if gap.numel():
+            margin = float(gap.min())
+    return top[:, :K], tv[:, :K], margin
+
+
+@torch.no_grad()
+def beam_decode_ids_reference_algorithm(model, feats: torch.Tensor, mask, beam_size: int, max_len: int = 30,
+                                        length_penalty: float = 1.0, return_all: bool = False):
+    """beam_decode_ids without the KV cache: every step re-runs the whole decoder (dec.decode_word) on the reordered [B*K, t]
+    histories and selects on the host in torch by the same rule.  Returns (result as beam_decode_ids, min margin): the smallest
+    gap between the K-th and (K+1)-th candidate value over every video and step (where a test may not expect ids to agree)."""
+    pre = model.cap_preprocessor
+    model._ps.refresh_shadow()
+    model._ps.refresh_lazy_transposed()
+    enc, dec = model.video_encoder._engine(), model.cap_decoder._engine()
+    K, V = int(beam_size), dec.V
+    if not 1 <= K <= 16 or K > V:
+        raise ValueError(f"beam_size must be in 1..16 and <= the vocabulary size, got {beam_size}")
+    B, T = feats.shape[0], feats.shape[1]
+    M, Te, dev = B * K, T + 1, feats.device
+    mem = enc.forward(feats, mask, False)
+    d = mem.shape[-1]
+    mem_rep = mem.reshape(B, 1, Te, d).expand(-1, K, -1, -1).reshape(M * Te, d).contiguous()
+    hist = torch.full((M, 1), pre.start_id, dtype=torch.long, device=dev)
+    s = torch.full((B, K), float("-inf"), dtype=torch.float32, device=dev)
+    s[:, 0] = 0.0
+    s = s.reshape(M)
+    fin = torch.zeros(M, dtype=torch.bool, device=dev)
+    rows = torch.arange(B, device=dev)[:, None] * K
+    min_margin = float("inf")
+    for _ in range(max_len - 1):
+        logits = dec.decode_word(mem_rep, M, Te, hist).float()
+        logp = logits - torch.logsumexp(logits, dim=1, keepdim=True)
+        vals = s[:, None] + logp
+        valid = (~fin)[:, None].expand(-1, V).clone()
+        frozen = torch.full_like(vals, float("-inf"))
+        frozen[:, pre.pad_id] = s
+        vals = torch.where(fin[:, None], frozen, vals)
+        valid[fin, pre.pad_id] = True
+        flat, val, margin = _select_ref(vals.view(B, K * V), valid.view(B, K * V), K)
+        min_margin = min(min_margin, margin)
+        parent = (rows + flat // V).reshape(M)
+        tok = (flat % V).reshape(M)
+        hist = torch.cat([hist[parent], tok[:, None]], 1)
+        s = val.reshape(M)
+        fin = fin[parent] | (tok == pre.end_id)
+        if bool(fin.all()):
+            break
+    return _beam_finish(hist, s, B, K, pre.end_id, length_penalty, return_all), min_margin

@@ -1240,6 +1240,11 @@ class DecodeState:
         self.graphs = {}
 
 
+def _greedy_stage(self, st: DecodeState, logits: torch.Tensor, t: int, end_id: int):
+    """Selection stage of a greedy step: arg-max into column t + sticky end flags + the first step at which every row has ended."""
+    ops.greedy_select(logits, st.ys[:, t], end_id, st.ended, st.ended_count, st.all_ended_at, t, cols=self.V)
+
+
 def _decoder_decode_begin(self, st: DecodeState, mem: torch.Tensor, start_id: int, pad_id: int):
     """Encoder memory -> cross-attention K/V of every layer (once per decode); reset ids / cache."""
     d = self.cfg["d"]
@@ -1253,7 +1258,7 @@ def _decoder_decode_begin(self, st: DecodeState, mem: torch.Tensor, start_id: in
         ops.gemm(mem, self.W(lp + "in_proj_weight")[d:], st.kv_cross[l], bias=self.F(lp + "in_proj_bias")[d:])
 
 
-def _decoder_decode_step(self, st: DecodeState, t: int, end_id: int):
+def _decoder_decode_step(self, st: DecodeState, t: int, end_id: int, select=None):
     """One greedy step with the KV cache: consumes token ys[:, t-1], writes ys[:, t].  Equivalent to
     CapDecoder.decode_word on ys[:, :t] + torch.max (CapDecoder.py:62-79, MMT4Caption.py:164-172): the
     keys/values of positions < t-1 are the cached projections of the same inputs."""
@@ -1292,9 +1297,9 @@ def _decoder_decode_step(self, st: DecodeState, t: int, end_id: int):
     y = self._ln_fwd(b, "nf.", "decoder.norm.", x, None, None)
     logits = b.get("logits", (Bn, self.Vp), self.dt)
     ops.gemm(y, self.W("generator.weight"), logits, bias=self.F("generator.bias"), n_valid=self.V, workspace=ws)
-    # arg-max into column t + sticky end flags + the first step at which every row has ended: one launch, no host sync
+    # selection (greedy: arg-max into column t + sticky end flags + the first step at which every row has ended: one launch), no host sync
     st.last_logits = logits          # [B, Vp] of this step (decode.teacher_forced_next_ids reads it)
-    ops.greedy_select(logits, st.ys[:, t], end_id, st.ended, st.ended_count, st.all_ended_at, t, cols=self.V)
+    (select or _greedy_stage)(self, st, logits, t, end_id)
 
 
 def _decoder_small_decode_ok(self, st: DecodeState) -> bool:
@@ -1315,7 +1320,7 @@ def _decoder_small_decode_ok(self, st: DecodeState) -> bool:
             and st.Lmax <= 64 and st.Te <= 64 and self.dev.type == "cuda")
 
 
-def _decoder_decode_step_small(self, st: DecodeState, t: int, end_id: int):
+def _decoder_decode_step_small(self, st: DecodeState, t: int, end_id: int, select=None):
     """The same step as _decoder_decode_step in 6 launches per layer + 2: embedding, LayerNorms and both attention cores run in the
     prologues of the matrix-vector kernels that consume them, residual adds in the epilogues of the producers; activations
     between stages are fp32 vectors (pre-norm sums s, normalised x kept for the next residual)."""
@@ -1356,7 +1361,7 @@ def _decoder_decode_step_small(self, st: DecodeState, t: int, end_id: int):
     ops.decode_gemv(self.W("generator.weight"), logits, B, bias=self.F("generator.bias"), pro="ln_ln", x_in=s3, ln1=prev_norm,
                     ln2=(self.F("decoder.norm.weight"), self.F("decoder.norm.bias")), n_valid=self.V)
     st.last_logits = logits          # [B, Vp] of this step (decode.teacher_forced_next_ids reads it)
-    ops.greedy_select(logits, st.ys[:, t], end_id, st.ended, st.ended_count, st.all_ended_at, t, cols=self.V)
+    (select or _greedy_stage)(self, st, logits, t, end_id)
 
 
 def _decoder_block_decode_ok(self, st: DecodeState) -> bool:
@@ -1418,7 +1423,7 @@ def _decoder_fused_decode_ok(self, st: DecodeState) -> bool:
             and self.dev.type == "cuda")
 
 
-def _decoder_decode_step_fused(self, st: DecodeState, t: int, end_id: int):
+def _decoder_decode_step_fused(self, st: DecodeState, t: int, end_id: int, select=None):
     """The same step as _decoder_decode_step in 8 launches per layer + 3 instead of 11 + 4: every projection is one skinny MFMA
     kernel (M = batch rows, K split over the waves); norm1 / norm2 / norm3 run as the prologue of the projection that consumes
     them (which also stores the normalised rows once, for the residual two launches later), the residual adds in the epilogues;
@@ -1463,17 +1468,72 @@ def _decoder_decode_step_fused(self, st: DecodeState, t: int, end_id: int):
     logits = b.get("logits", (Bn, self.Vp), self.dt)
     ops.gemm(y, self.W("generator.weight"), logits, bias=self.F("generator.bias"), n_valid=self.V, workspace=self.gemm_ws())
     st.last_logits = logits          # [B, Vp] of this step (decode.teacher_forced_next_ids reads it)
-    ops.greedy_select(logits, st.ys[:, t], end_id, st.ended, st.ended_count, st.all_ended_at, t, cols=self.V)
+    (select or _greedy_stage)(self, st, logits, t, end_id)
 
 
-def _decoder_decode_step_any(self, st: DecodeState, t: int, end_id: int):
-    if _decoder_block_decode_ok(self, st):
+def _decoder_decode_step_any(self, st: DecodeState, t: int, end_id: int, select=None):
+    """select: the selection stage at the end of the step, (engine, state, logits, t, end_id) -> None; None = greedy.  The batch-1
+    block step fuses greedy selection into its generator launch: any other stage takes the gemv / fused / generic step."""
+    if select is None and _decoder_block_decode_ok(self, st):
         return _decoder_decode_step_block(self, st, t, end_id)
     if _decoder_small_decode_ok(self, st):
-        return _decoder_decode_step_small(self, st, t, end_id)
+        return _decoder_decode_step_small(self, st, t, end_id, select)
     if _decoder_fused_decode_ok(self, st):
-        return _decoder_decode_step_fused(self, st, t, end_id)
-    return _decoder_decode_step(self, st, t, end_id)
+        return _decoder_decode_step_fused(self, st, t, end_id, select)
+    return _decoder_decode_step(self, st, t, end_id, select)
+
+
+class BeamDecodeState(DecodeState):
+    """Static buffers of one beam-search session (B videos, K beams, Te, Lmax): the greedy session's buffers for M = B*K rows
+    (row b*K + k = beam k of video b) with the self-attention cache as a PING-PONG pair [2][L, M*Lmax, 3d] (step t runs on side
+    t % 2, and vct_beam_reorder gathers the slots < t of every row's parent into the other side), the memory replicated per
+    beam (cross-attention K/V per row), and the beam state: scores fp32 [M], finished uint8 [M], parent rows int32 [Lmax, M]
+    (row t: the parent of every slot chosen at step t; ids are back-tracked once at the end), ys = the token table (column t:
+    the token appended at step t), per-step finished counters int32 [Lmax], all_ended_at = the first step after which every
+    slot is finished."""
+
+    def __init__(self, eng: "DecoderEngine", Bv: int, K: int, Te: int, Lmax: int):
+        super().__init__(eng, Bv * K, Te, Lmax)
+        d, L, dt, dev = eng.cfg["d"], eng.cfg["layers"], eng.dt, eng.dev
+        M = Bv * K
+        self.Bv, self.K = Bv, K
+        self.kv_self = None
+        self.kv_layers = [torch.zeros(L, M * Lmax, 3 * d, dtype=dt, device=dev) for _ in range(2)]
+        self.mem_rep = torch.empty(M * Te, d, dtype=dt, device=dev)
+        self.scores = torch.zeros(M, dtype=torch.float32, device=dev)
+        self.finished = torch.zeros(M, dtype=torch.uint8, device=dev)
+        self.parents = torch.zeros(Lmax, M, dtype=torch.int32, device=dev)
+        self.fin_count = torch.zeros(Lmax, dtype=torch.int32, device=dev)
+        nws = ops.beam_select_workspace_bytes(torch.float32, Bv, K, eng.V) // 4     # fp32 logits (the gemv step's) need the most
+        self.sel_ws = torch.empty(max(nws, 1), dtype=torch.float32, device=dev)
+        self.pad_id = None
+
+
+def _decoder_beam_begin(self, st: BeamDecodeState, mem: torch.Tensor, start_id: int, pad_id: int):
+    """_decoder_decode_begin on the memory replicated to every beam's row + the beam state of step 0: slot 0 of every video
+    scores 0, the others -inf (so step 1 expands slot 0 only), nothing finished."""
+    d, Te = self.cfg["d"], st.Te
+    st.mem_rep.view(st.Bv, st.K, Te, d).copy_(mem.reshape(st.Bv, 1, Te, d).expand(-1, st.K, -1, -1))
+    _decoder_decode_begin(self, st, st.mem_rep, start_id, pad_id)
+    st.pad_id = int(pad_id)
+    st.scores.fill_(float("-inf"))
+    st.scores.view(st.Bv, st.K)[:, 0] = 0.0
+    st.finished.zero_()
+    st.fin_count.zero_()
+
+
+def _beam_stage(self, st: BeamDecodeState, logits: torch.Tensor, t: int, end_id: int):
+    """Selection stage of a beam step: top K per video (vct_beam_select), then the cache slots < t follow their parents into the
+    other side of the ping-pong pair (vct_beam_reorder)."""
+    ops.beam_select(logits, st.Bv, st.K, st.scores, st.finished, st.parents[t], st.ys[:, t], end_id, st.pad_id,
+                    st.fin_count[t:t + 1], st.all_ended_at, t, st.sel_ws, cols=self.V)
+    ops.beam_reorder(st.kv_layers[t % 2], st.kv_layers[(t + 1) % 2], st.parents[t], st.B, st.Lmax, self.cfg["d"], t)
+
+
+def _decoder_beam_step(self, st: BeamDecodeState, t: int, end_id: int):
+    """One beam step: the decode step of M = B*K rows on cache side t % 2, with the beam selection stage."""
+    st.kv_self = list(st.kv_layers[t % 2].unbind(0))
+    return _decoder_decode_step_any(self, st, t, end_id, select=_beam_stage)
 
 
 # A/B switch: vocabulary dX through a transposed weight shadow (NT form on the persistent 256x256 kernel, split over K).  The shadow is
@@ -1495,3 +1555,5 @@ DecoderEngine.block_decode = os.environ.get("VCT_BLOCK_DECODE", "1") != "0"   # 
 DecoderEngine.small_batch_decode = True       # A/B switch: weight-streaming GEMV step for batch <= 4
 DecoderEngine.decode_begin = _decoder_decode_begin
 DecoderEngine.decode_step = _decoder_decode_step_any
+DecoderEngine.beam_begin = _decoder_beam_begin
+DecoderEngine.beam_step = _decoder_beam_step

@@ -15,31 +15,40 @@ def _strip_special(s: str) -> str:
 
 
 @torch.no_grad()
-def v2t_batch(model, video_feats: Sequence[torch.Tensor], video_masks: Optional[Sequence[torch.Tensor]], max_len: int = 30) -> List[str]:
-    """eval.py:126-145: video_feats = list (one per modality) of [B, T, E]; masks = list of bool [B, T] or None."""
+def _decode(model, feats, masks, max_len, beam_size):
+    if beam_size is None:
+        return model.greedy_decode(feats, masks, max_len=max_len)
+    return model.beam_decode(feats, masks, beam_size=beam_size, max_len=max_len)
+
+
+@torch.no_grad()
+def v2t_batch(model, video_feats: Sequence[torch.Tensor], video_masks: Optional[Sequence[torch.Tensor]], max_len: int = 30,
+              beam_size: Optional[int] = None) -> List[str]:
+    """eval.py:126-145: video_feats = list (one per modality) of [B, T, E]; masks = list of bool [B, T] or None.
+    beam_size: None = greedy (the reference's only mode), else beam search with that many beams (MMT4Caption.beam_decode)."""
     model.eval()
     dev = model.device
     video_feats = [f.to(dev, non_blocking=True) for f in video_feats]
     video_masks = [m.to(dev, non_blocking=True) for m in video_masks] if video_masks is not None else None
-    return [_strip_special(r) for r in model.greedy_decode(video_feats, video_masks, max_len=max_len)]
+    return [_strip_special(r) for r in _decode(model, video_feats, video_masks, max_len, beam_size)]
 
 
 @torch.no_grad()
-def v2t_single(model, video_feat: Sequence[torch.Tensor], max_len: int = 30) -> str:
+def v2t_single(model, video_feat: Sequence[torch.Tensor], max_len: int = 30, beam_size: Optional[int] = None) -> str:
     """train.py:194-203: one video (list of [T, E] per modality), no mask."""
     model.eval()
     feats = [f.unsqueeze(0).to(model.device) for f in video_feat]
-    return _strip_special(model.greedy_decode(feats, max_len=max_len)[0])
+    return _strip_special(_decode(model, feats, None, max_len, beam_size)[0])
 
 
 @torch.no_grad()
-def eval_epoch(model, dataloader, max_len: int = 30) -> Dict[str, str]:
+def eval_epoch(model, dataloader, max_len: int = 30, beam_size: Optional[int] = None) -> Dict[str, str]:
     """train.py:171-180 / eval.py:156-160 without the scorer: captions for every video a by_video loader yields
     -> {vid: caption}.  Decoding is batched (the reference's eval config uses batch_size 1)."""
     model.eval()
     vid2result: Dict[str, str] = {}
     for v_feats, v_masks, _caps, vids in dataloader:
-        vid2result.update(zip(vids, v2t_batch(model, v_feats, v_masks, max_len=max_len)))
+        vid2result.update(zip(vids, v2t_batch(model, v_feats, v_masks, max_len=max_len, beam_size=beam_size)))
     return vid2result
 
 

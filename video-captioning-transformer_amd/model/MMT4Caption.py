@@ -258,7 +258,9 @@ class MMT4Caption(nn.Module):
     @torch.no_grad()
     def greedy_decode(self, video_feat: List[torch.Tensor], video_masks: Optional[List[torch.Tensor]] = None,
                       max_len: int = 30) -> List[str]:
-        ys = self.greedy_decode_ids(video_feat, video_masks, max_len)
+        return self._ids_to_captions(self.greedy_decode_ids(video_feat, video_masks, max_len))
+
+    def _ids_to_captions(self, ys: torch.Tensor) -> List[str]:
         end_id = self.cap_preprocessor.end_id
         result = []
         for idx_cap in ys.tolist():
@@ -288,8 +290,30 @@ class MMT4Caption(nn.Module):
         finally:
             self.train(was_training)
 
-    def beam_decode(self):
-        pass
+    @torch.no_grad()
+    def beam_decode(self, video_feat: List[torch.Tensor], video_masks: Optional[List[torch.Tensor]] = None, beam_size: int = 5,
+                    max_len: int = 30, length_penalty: float = 1.0) -> List[str]:
+        """Beam-search captions, one string per video (the reference's beam_decode is `pass`, MMT4Caption.py:186); ids -> text
+        as greedy_decode.  Semantics: decode.beam_decode_ids."""
+        return self._ids_to_captions(self.beam_decode_ids(video_feat, video_masks, beam_size, max_len, length_penalty))
+
+    @torch.no_grad()
+    def beam_decode_ids(self, video_feat, video_masks=None, beam_size: int = 5, max_len: int = 30, length_penalty: float = 1.0,
+                        kv_cache: bool = True, use_graphs: bool = True, return_all: bool = False):
+        """The best beam's id matrix [B, <=max_len] (return_all: (ids [B, K, L'], final scores [B, K])) of beam_decode.
+        kv_cache=False runs the reference algorithm (full decoder re-run per token, host-side selection)."""
+        was_training = self.training
+        self.eval()
+        try:
+            from .. import decode
+            mask = video_masks[0] if video_masks is not None else None
+            if kv_cache:
+                return decode.beam_decode_ids(self, video_feat[0], mask, beam_size, max_len, length_penalty,
+                                              use_graphs=use_graphs, return_all=return_all)
+            return decode.beam_decode_ids_reference_algorithm(self, video_feat[0], mask, beam_size, max_len, length_penalty,
+                                                              return_all=return_all)[0]
+        finally:
+            self.train(was_training)
 
     def mode(self, forward_type="caption") -> None:
         self.f_type = forward_type

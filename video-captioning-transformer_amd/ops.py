@@ -517,6 +517,28 @@ def greedy_select(x, out, end_id: int, ended, ended_count, all_ended_at, t: int,
     return out
 
 
+def beam_select_workspace_bytes(dtype, B: int, K: int, V: int) -> int:
+    """Workspace of vct_beam_select (include/vct_hip.h): chunk partials of every row."""
+    chunk = 256 * (8 if dtype == torch.bfloat16 else 4)
+    return B * K * ((V + chunk - 1) // chunk) * (2 + 2 * K) * 4
+
+
+def beam_select(x, B: int, K: int, scores, finished, parent, out, end_id: int, pad_id: int, finished_count, all_finished_at,
+                t: int, ws, cols=None):
+    """One beam-search selection step (include/vct_hip.h, vct_beam_select): the K best continuations of each video's K beams
+    -> parent rows, tokens into `out` (column t of the token table), scores / finished flags in place, stop bookkeeping."""
+    L.check(L.load().vct_beam_select(L.dtype_code(x.dtype), int(B), int(K), int(cols or x.shape[1]), x.data_ptr(), _ld(x),
+                                     scores.data_ptr(), finished.data_ptr(), parent.data_ptr(), out.data_ptr(), out.stride(0),
+                                     int(end_id), int(pad_id), finished_count.data_ptr(), all_finished_at.data_ptr(), int(t),
+                                     ws.data_ptr(), ws.numel() * ws.element_size(), L.stream_ptr()), "vct_beam_select")
+
+
+def beam_reorder(src, dst, parent, M: int, Lmax: int, d: int, t: int):
+    """Slots < t of every layer's self-attention cache follow their beam's parent row (vct_beam_reorder): src / dst [L, M * Lmax, 3d]."""
+    L.check(L.load().vct_beam_reorder(L.dtype_code(src.dtype), src.shape[0], int(M), int(Lmax), int(d), int(t), parent.data_ptr(),
+                                      src.data_ptr(), dst.data_ptr(), src.stride(0), L.stream_ptr()), "vct_beam_reorder")
+
+
 def decode_gemv(W, out, B, *, bias=None, pro="none", x_in=None, ln1=None, ln2=None, embed=None, attn=None, act=None, res=None,
                 out_native=False, ld_out=None, x_out=None, n_valid=None):
     """One stage of the small-batch greedy-decode step (include/vct_hip.h, vct_decode_gemv).  W [N, K]; out: tensor whose row b starts
