@@ -296,6 +296,38 @@ int vct_enc_frontend_fwd(int dtype, int B, int T, int d, const void* u, const fl
 int vct_enc_frontend_bwd(int dtype, int B, int T, int d, const void* dz, void* du, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Multi-modal encoder front end (n = 2 .. VCT_MM_MAX_MODAL feature streams) after the per-modality `unify` GEMMs
+ * (csrc/vct_mm_frontend.hip).  Memory rows: modality i owns rows off_i .. off_i + T_i, off_i = sum_{j<i} (T_j + 1), S = off_n;
+ * its row off_i is the aggregation row.
+ *   fwd: x0[b, off_i]       = (temp[off_i] + modal_w[labels[off_i]]) + mean_t u_i[b, t]   (fp32 mean over all T_i rows, pads included)
+ *        x0[b, off_i+1+t]   = (temp[off_i+1+t] + modal_w[labels[off_i+1+t]]) + u_i[b, t]
+ *        key_pad[b, off_i] = 0, key_pad[b, off_i+1+t] = mask_i[b, t] (0 when mask_i is NULL); key_pad may be NULL.
+ *   bwd: du_i[b, t] = dx[b, off_i+1+t] + dx[b, off_i] / T_i;  d_modal[l, :] = sum over b and the rows s with labels[s] == l of
+ *        dx[b, s, :] -- WRITTEN (not accumulated), fp32, in a fixed order (no atomics: bitwise reproducible).
+ * u_i / x0 / dx / du_i: dtype rows of d (16-byte aligned, d a multiple of 8 bf16 / 4 fp32); temp fp32 [S, d] (aggregation rows 0);
+ * modal_w fp32 [n_labels, d]; labels int32 [S] in [0, n_labels) (not checked on the device: a row with a label outside it gets no
+ * modal row and contributes to no d_modal row; the caller validates its table); n_labels = n or 2n; S <= 1024 here, but the
+ * attention kernels that read x0 take S <= 64 (vct_attn_desc: Lq, Lk <= 64) and the sample-stationary stack S <= 32.
+ * replaces: GlobalAggregation('avg') + cat + TemporalEncoding + ModalEmbedding + `temp + modal + feats` and the mask cat of
+ * MultiModalEncoder.forward (MMEncoder.py:12-48,83-104,244-276), and their autograd backward.  One launch each.
+ * --------------------------------------------------------------------------------------------- */
+#define VCT_MM_MAX_MODAL 8
+typedef struct vct_mm_frontend_desc {
+  int32_t dtype, n, B, d;
+  int32_t n_labels, reserved;
+  int32_t T[VCT_MM_MAX_MODAL];
+  const void* u[VCT_MM_MAX_MODAL];          /* fwd: [B*T_i, d] */
+  const uint8_t* mask[VCT_MM_MAX_MODAL];    /* fwd: [B, T_i] (1 = padded) or NULL */
+  const float* temp; const float* modal_w; const int32_t* labels;
+  void* x0; uint8_t* key_pad;               /* fwd outputs: [B*S, d], [B, S] */
+  const void* dx;                           /* bwd: [B*S, d] */
+  void* du[VCT_MM_MAX_MODAL];               /* bwd: [B*T_i, d] */
+  float* d_modal;                           /* bwd: [n_labels, d] */
+} vct_mm_frontend_desc;
+int vct_mm_frontend_fwd(const vct_mm_frontend_desc* d, void* stream);
+int vct_mm_frontend_bwd(const vct_mm_frontend_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Token embedding: x[n] = dropout(table[ids[n]] + pos[n % S])   (no sqrt(d) scaling)
  * replaces: nn.Embedding(padding_idx) + PositionalEmbedding (CapDecoder.py:26,48; Embedding.py:23-25).
  * ids: int64 [N] read with element stride id_stride from ids + b*id_batch_stride (so the token-shift

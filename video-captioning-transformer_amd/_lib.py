@@ -110,6 +110,17 @@ class DecodeBlockDesc(C.Structure):
                 ("sel_ws", vp), ("tok_out", vp), ("end_id", i64), ("ended", vp), ("ended_count", vp), ("all_ended_at", vp), ("t", i32), ("pad1", i32)]
 
 
+MM_MAX_MODAL = 8
+
+
+class MmFrontendDesc(C.Structure):
+    """include/vct_hip.h, vct_mm_frontend_desc: the multi-modal encoder front end."""
+    _fields_ = [("dtype", i32), ("n", i32), ("B", i32), ("d", i32), ("n_labels", i32), ("reserved", i32),
+                ("T", i32 * MM_MAX_MODAL), ("u", vp * MM_MAX_MODAL), ("mask", vp * MM_MAX_MODAL),
+                ("temp", vp), ("modal_w", vp), ("labels", vp), ("x0", vp), ("key_pad", vp), ("dx", vp),
+                ("du", vp * MM_MAX_MODAL), ("d_modal", vp)]
+
+
 DEC_PRO = {"none": 0, "embed": 1, "ln": 2, "ln_ln": 3, "self_attn": 4, "cross_attn": 5}
 
 _SIGS = {
@@ -135,6 +146,8 @@ _SIGS = {
     "vct_ln_param_finalize_batched": (C.c_int, [vp, C.c_int, C.c_int, vp]),
     "vct_enc_frontend_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
     "vct_enc_frontend_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "vct_mm_frontend_fwd": (C.c_int, [C.POINTER(MmFrontendDesc), vp]),
+    "vct_mm_frontend_bwd": (C.c_int, [C.POINTER(MmFrontendDesc), vp]),
     "vct_embed_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, vp, vp, vp, u32, f32, vp]),
     "vct_embed_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, i64, vp, vp, vp, i64, C.c_int, vp, u32, f32, vp]),
     "vct_sce_loss": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, i64, f32, vp, vp, i64, vp, vp]),

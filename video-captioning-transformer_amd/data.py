@@ -167,13 +167,17 @@ class DeviceLoader:
 
     def __init__(self, dataset: CaptionDataset, batch_size: int, preprocessor, device, shuffle: bool = False,
                  rank: int = 0, world: int = 1, seed: int = 0, drop_last: bool = False, feat_dtype=torch.float32):
-        if len(dataset.video_feat_dirs) != 1:
-            raise NotImplementedError("the accelerated caption path takes one modality (MMEncoder with a single feature stream)")
         self.ds, self.bs, self.device, self.shuffle = dataset, batch_size, torch.device(device), shuffle
         self.rank, self.world, self.seed, self.drop_last, self.epoch = rank, world, seed, drop_last, 0
         self.feat_dtype = feat_dtype
+        # one store per modality (data.*.feat_dir lists one directory per feature stream), clips in the same order
+        self.stores = [FeatureStore([p[m] for p in dataset.video_feat_list]).to(self.device)
+                       for m in range(len(dataset.video_feat_dirs))]
+        self.store = self.stores[0]
+        for st in self.stores[1:]:
+            if st.stems != self.store.stems:
+                raise ValueError("the feature directories of the modalities hold different clips (file stems differ)")
         paths = [p[0] for p in dataset.video_feat_list]
-        self.store = FeatureStore(paths).to(self.device)
         row = {s: i for i, s in enumerate(self.store.stems)}
         if dataset.mode == "by_caption":
             self.clip_of_item = np.array([row[p[0].stem] for _c, p in dataset.cap_vid_list], dtype=np.int64)
@@ -216,10 +220,10 @@ class DeviceLoader:
             item_h, item_d = order[a:a + self.bs], order_dev[a:a + self.bs]
             clip_h = self.clip_of_item[item_h]
             clip_d = self.clip_of_item_dev.index_select(0, item_d)
-            feat, mask = self.store.gather(clip_h, clip_d, self.feat_dtype)
+            feats, masks = zip(*[st.gather(clip_h, clip_d, self.feat_dtype) for st in self.stores])
             if self.ids is not None:
                 S = int(self.cap_len[item_h].max())
                 caps = self.ids.index_select(0, item_d)[:, :S]
             else:
                 caps = tuple("" for _ in item_h)
-            yield [feat], [mask], caps, tuple(self.store.stems[i] for i in clip_h)
+            yield list(feats), list(masks), caps, tuple(self.store.stems[i] for i in clip_h)

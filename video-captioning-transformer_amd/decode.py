@@ -16,8 +16,14 @@ predict_video.py:170's `--beam` says "not support yet"); the semantics are state
 import torch
 
 from . import ops
-from .engine import BeamDecodeState, DecodeState
+from .engine import BeamDecodeState, DecodeState, first_input as _first, memory_len, stage_inputs, static_inputs
 from .utils import capture_graph
+
+
+def _inputs_key(feats, mask):
+    if isinstance(feats, (list, tuple)):
+        return (tuple((tuple(f.shape), f.dtype) for f in feats), mask is not None)
+    return (tuple(feats.shape), feats.dtype, mask is not None)
 
 
 @torch.no_grad()
@@ -26,14 +32,14 @@ def greedy_decode_ids_reference_algorithm(model, feats: torch.Tensor, mask, max_
     model._ps.refresh_shadow()
     model._ps.refresh_lazy_transposed()
     enc, dec = model.video_encoder._engine(), model.cap_decoder._engine()
-    B, T = feats.shape[0], feats.shape[1]
+    B, Te, dev = _first(feats).shape[0], memory_len(feats), _first(feats).device
     mem = enc.forward(feats, mask, False)
-    ys = torch.full((B, max_len), pre.pad_id, dtype=torch.long, device=feats.device)
+    ys = torch.full((B, max_len), pre.pad_id, dtype=torch.long, device=dev)
     ys[:, 0] = pre.start_id
-    ended = torch.zeros(B, dtype=torch.bool, device=feats.device)
+    ended = torch.zeros(B, dtype=torch.bool, device=dev)
     t = 1
     for _ in range(max_len - 1):
-        logits = dec.decode_word(mem, B, T + 1, ys[:, :t])
+        logits = dec.decode_word(mem, B, Te, ys[:, :t])
         ops.argmax_rows(logits, ys[:, t], cols=dec.V)
         ended |= ys[:, t] == pre.end_id
         t += 1
@@ -63,8 +69,7 @@ def greedy_decode_ids(model, feats: torch.Tensor, mask, max_len: int = 30, use_g
     stream issued once the host has seen THAT step's event complete) -- the reference syncs on every token (`.tolist()`, MMT4Caption.py:168).  A
     caption batch that ends at step s therefore costs at most s + lookahead steps; the id matrix is truncated at s."""
     dec = model.cap_decoder._engine()
-    B, T = feats.shape[0], feats.shape[1]
-    st = _session(model, dec, B, T + 1, max_len)
+    st = _session(model, dec, _first(feats).shape[0], memory_len(feats), max_len)
     stop = _run_session(model, st, feats, mask, max_len, use_graphs, sync_every, lookahead, dec.decode_begin, dec.decode_step)
     return st.ys[:, :stop + 1].clone()
 
@@ -79,32 +84,28 @@ def _run_session(model, st, feats, mask, max_len, use_graphs, sync_every, lookah
     stamp = model._ps._stamp
     if st.__dict__.get("weights_stamp") != stamp:      # graphs bake weight pointers only, but keep it simple and safe
         st.weights_stamp = stamp
-    on_gpu = feats.device.type == "cuda"
+    on_gpu = _first(feats).device.type == "cuda"
     if on_gpu and st.__dict__.get("poll_stream") is None:
-        st.poll_stream = torch.cuda.Stream(device=feats.device)
+        st.poll_stream = torch.cuda.Stream(device=_first(feats).device)
         st.poll_host = torch.empty(1, dtype=torch.long).pin_memory()
         st.events = [torch.cuda.Event() for _ in range(max_len)]
     if use_graphs and on_gpu:
         # the prologue (encoder forward over the batch, cross-attention K/V of the memory for every layer, cache / flag reset:
         # ~40 launches, host-bound at 0.33 ms when issued one by one) is ONE captured graph too; the inputs go through static
         # copies.  It bakes pointers into the engines' shared grow-only buffers: re-captured whenever any of them grew.
-        key = (tuple(feats.shape), feats.dtype, mask is not None)
+        key = _inputs_key(feats, mask)
         bg = st.__dict__.get("begin")
         if bg is None or bg["key"] != key or bg["gen"] != model._ps.ctx.generation:
-            fin = torch.empty_like(feats, memory_format=torch.contiguous_format)
-            min_ = torch.empty_like(mask, memory_format=torch.contiguous_format) if mask is not None else None
-            fin.copy_(feats)
-            if mask is not None:
-                min_.copy_(mask)
+            fin, min_ = static_inputs(feats, True), static_inputs(mask, True)
             begin(st, enc.forward(fin, min_, False), pre.start_id, pre.pad_id)      # warm-up: allocates
             g = torch.cuda.CUDAGraph()
             with capture_graph(g):
                 begin(st, enc.forward(fin, min_, False), pre.start_id, pre.pad_id)
             st.begin = {"key": key, "gen": model._ps.ctx.generation, "g": g, "fin": fin, "min": min_}
         else:
-            bg["fin"].copy_(feats)
+            stage_inputs(bg["fin"], feats)
             if mask is not None:
-                bg["min"].copy_(mask)
+                stage_inputs(bg["min"], mask)
             bg["g"].replay()
     else:
         begin(st, enc.forward(feats, mask, False), pre.start_id, pre.pad_id)
@@ -164,11 +165,11 @@ def teacher_forced_next_ids(model, feats: torch.Tensor, mask, prefix_ids: torch.
     model._ps.refresh_shadow()
     model._ps.refresh_lazy_transposed()
     enc, dec = model.video_encoder._engine(), model.cap_decoder._engine()
-    B, T = feats.shape[0], feats.shape[1]
-    st = DecodeState(dec, B, T + 1, steps + 1)
+    B, dev = _first(feats).shape[0], _first(feats).device
+    st = DecodeState(dec, B, memory_len(feats), steps + 1)
     dec.decode_begin(st, enc.forward(feats, mask, False), pre.start_id, pre.pad_id)
-    out = torch.empty(B, steps, dtype=torch.long, device=feats.device)
-    logits = torch.empty(B, steps, dec.V, dtype=torch.float32, device=feats.device) if return_logits else None
+    out = torch.empty(B, steps, dtype=torch.long, device=dev)
+    logits = torch.empty(B, steps, dec.V, dtype=torch.float32, device=dev) if return_logits else None
     for t in range(1, steps + 1):
         st.ys[:, t - 1] = prefix_ids[:, t - 1]
         dec.decode_step(st, t, pre.end_id)
@@ -233,14 +234,14 @@ def beam_decode_ids(model, feats: torch.Tensor, mask, beam_size: int, max_len: i
     K = int(beam_size)
     if not 1 <= K <= 16 or K > dec.V:
         raise ValueError(f"beam_size must be in 1..16 and <= the vocabulary size, got {beam_size}")
-    B, T = feats.shape[0], feats.shape[1]
-    st = _beam_session(model, dec, B, K, T + 1, max_len)
+    B, dev = _first(feats).shape[0], _first(feats).device
+    st = _beam_session(model, dec, B, K, memory_len(feats), max_len)
     stop = _run_session(model, st, feats, mask, max_len, use_graphs, sync_every, lookahead, dec.beam_begin, dec.beam_step)
     # back-track the parent rows once: column t of slot j is the token appended at step t by the slot's ancestor
     M = B * K
-    ids = torch.empty(M, stop + 1, dtype=torch.long, device=feats.device)
+    ids = torch.empty(M, stop + 1, dtype=torch.long, device=dev)
     ids[:, 0] = pre.start_id
-    r = torch.arange(M, device=feats.device)
+    r = torch.arange(M, device=dev)
     for t in range(stop, 0, -1):
         ids[:, t] = st.ys[r, t]
         r = st.parents[t].long()[r]
@@ -279,8 +280,8 @@ def beam_decode_ids_reference_algorithm(model, feats: torch.Tensor, mask, beam_s
     K, V = int(beam_size), dec.V
     if not 1 <= K <= 16 or K > V:
         raise ValueError(f"beam_size must be in 1..16 and <= the vocabulary size, got {beam_size}")
-    B, T = feats.shape[0], feats.shape[1]
-    M, Te, dev = B * K, T + 1, feats.device
+    B = _first(feats).shape[0]
+    M, Te, dev = B * K, memory_len(feats), _first(feats).device
     mem = enc.forward(feats, mask, False)
     d = mem.shape[-1]
     mem_rep = mem.reshape(B, 1, Te, d).expand(-1, K, -1, -1).reshape(M * Te, d).contiguous()

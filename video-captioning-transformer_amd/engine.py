@@ -29,6 +29,45 @@ DMEM_SYNC = 0      # named sync point (ops.sync_record / sync_wait): d(memory) i
 _CUS = {}
 
 
+# Encoder inputs ("feats" / "mask" below and in decode / trainer / MMT4Caption): one tensor (one modality) or a list with one tensor
+# per modality (masks: such a list, or None).
+def memory_len(feats) -> int:
+    """Encoder memory rows per sample: T + 1 for one modality (a tensor [B, T, E] or a one-element list), sum_i (T_i + 1) for a
+    list of modalities (MMEncoder.py:249-265)."""
+    if isinstance(feats, (list, tuple)):
+        return sum(int(f.shape[1]) + 1 for f in feats)
+    return int(feats.shape[1]) + 1
+
+
+def first_input(feats) -> torch.Tensor:
+    """The (first modality's) feature tensor: batch size, device and dtype of an encoder input."""
+    return feats[0] if isinstance(feats, (list, tuple)) else feats
+
+
+def static_inputs(x, contiguous: bool = False):
+    """A copy of an encoder input at addresses of its own (None stays None, lists element-wise): what recorded launch lists and
+    captured graphs read.  contiguous: dense row-major copies instead of clones that keep the strides."""
+    if x is None:
+        return None
+    if isinstance(x, (list, tuple)):
+        return [static_inputs(t, contiguous) for t in x]
+    if contiguous:
+        out = torch.empty_like(x, memory_format=torch.contiguous_format)
+        out.copy_(x)
+        return out
+    return x.clone()
+
+
+def stage_inputs(dst, src, non_blocking: bool = False):
+    """Copy an encoder input into buffers made by static_inputs, skipping a tensor that already IS its buffer (a producer that
+    writes its batches into them)."""
+    if isinstance(dst, list):
+        for a, b in zip(dst, src):
+            stage_inputs(a, b, non_blocking)
+    elif dst.data_ptr() != src.data_ptr():
+        dst.copy_(src, non_blocking=non_blocking)
+
+
 def _cu_count(dev) -> int:
     n = _CUS.get(dev)
     if n is None:
@@ -832,13 +871,15 @@ class _StackBase:
 
 
 class EncoderEngine(_StackBase):
-    """MultiModalEncoder (one modality, 'avg' aggregation token, sinusoidal temporal encoding):
-    model/MMEncoder.py:244-276."""
+    """MultiModalEncoder ('avg' aggregation token, sinusoidal temporal encoding; one modality, or n >= 2 with the modal
+    embedding): model/MMEncoder.py:12-48, 83-104, 244-276."""
 
     def __init__(self, ps, prefix, cfg, seed, pe_buffer: torch.Tensor):
         super().__init__(ps, prefix, cfg, seed)
         self.pe = pe_buffer  # [1, 512, d] fp32 buffer `temp_emb.pe`
         self._pe_rows = {}
+        self._mm_rows = {}
+        self.mm_Ts = None    # frame counts of the modalities of the current shape (None: one modality)
 
     def pe_rows(self, T):
         r = self._pe_rows.get(T)
@@ -850,8 +891,42 @@ class EncoderEngine(_StackBase):
             self._pe_rows[T] = r
         return r
 
-    def forward(self, feats: torch.Tensor, mask: Optional[torch.Tensor], training: bool) -> torch.Tensor:
-        """feats [B,T,Ein] fp32, mask [B,T] bool (True = padded) or None -> memory [B*(T+1), d]."""
+    def mm_rows(self, Ts):
+        """(temporal rows fp32 [S, d], row labels int32 [S]) of the multi-modal front end for the frame counts Ts, cached per Ts.
+        Row t of modality i gets pe[idx_i[t]], idx_i = linspace(0, T_0 - 1, T_i) as int32 (MMEncoder.py:89-104), its aggregation
+        row 0; labels: i on frame rows, i + n (modal_different) or i on the aggregation row (MMEncoder.py:35-46)."""
+        r = self._mm_rows.get(Ts)
+        if r is None:
+            import numpy as np
+            n, d, diff = len(Ts), self.cfg["d"], self.cfg.get("modal_different", True)
+            temp = torch.zeros(sum(t + 1 for t in Ts), d, dtype=torch.float32, device=self.dev)
+            labels, at = [], 0
+            for i, t in enumerate(Ts):
+                idx = torch.from_numpy(np.linspace(0, Ts[0] - 1, t).astype(np.int32).astype(np.int64)).to(self.dev)
+                temp[at + 1:at + 1 + t] = self.pe[0, idx, :]
+                labels += [i + n if diff else i] + [i] * t
+                at += t + 1
+            # the kernels take the table as given (a row with an out-of-range label gets no modal row and no gradient): check it here,
+            # once per shape, against the embedding it indexes -- every row of the table must be used, and nothing else
+            rows = self.F("modal_emb.modal_emb.weight").shape[0]
+            if sorted(set(labels)) != list(range(rows)):
+                raise ValueError(f"modal-embedding labels {sorted(set(labels))} do not cover the {rows} rows of modal_emb exactly "
+                                 f"(n = {n}, modal_different = {diff})")
+            r = self._mm_rows[Ts] = (temp, torch.tensor(labels, dtype=torch.int32).to(self.dev))
+        return r
+
+    def forward(self, feats, mask, training: bool) -> torch.Tensor:
+        """feats [B,T,Ein] fp32, mask [B,T] bool (True = padded) or None -> memory [B*(T+1), d].  A list of n >= 2 modalities
+        (feats [B,T_i,E_i], masks [B,T_i] or None) -> memory [B*S, d], S = sum_i (T_i + 1)."""
+        n = self.cfg.get("n_modal", 1)
+        got = len(feats) if isinstance(feats, (list, tuple)) else 1
+        if got != n:        # (a stream short would leave its unify / modal-embedding gradients unwritten: stale ones get stepped)
+            raise ValueError(f"the encoder has {n} feature stream(s), got {got}" + (" (a bare tensor)" if n > 1 and got == 1 else ""))
+        if isinstance(feats, (list, tuple)):
+            if n > 1:
+                return self._forward_mm(feats, mask, training)
+            feats, mask = feats[0], (mask[0] if mask is not None else None)
+        self.mm_Ts = None
         B, T, Ein = feats.shape
         d, L = self.cfg["d"], self.cfg["layers"]
         self.p_drop = self.cfg["dropout"] if training else 0.0
@@ -886,7 +961,51 @@ class EncoderEngine(_StackBase):
         u = b.get("u", (B * T, d), self.dt)
         ops.gemm(x_in, self.W("unify.0.weight"), u, bias=self.F("unify.0.bias"))
         x = ops.enc_frontend_fwd(u, self.pe_rows(T), b.get("x0", (M, d), self.dt), B, T)
-        if self._ss_ok(Te, 0, B):       # (features of another width: the front end stays on its own kernels)
+        return self._stack_fwd(b, x, B, Te, kpm)      # (features of another width: the front end stays on its own kernels)
+
+    def _forward_mm(self, feats, masks, training: bool) -> torch.Tensor:
+        """n >= 2 modalities: per-modality input cast and unify GEMM, ONE front-end launch (vct_mm_frontend_fwd: aggregation rows,
+        temporal rows, modal embedding, the [B, S] key padding), then the stack (MMEncoder.py:244-274)."""
+        B = feats[0].shape[0]
+        Ts = tuple(int(f.shape[1]) for f in feats)
+        d = self.cfg["d"]
+        S = sum(t + 1 for t in Ts)
+        if any(f.shape[0] != B for f in feats) or (masks is not None and len(masks) != len(feats)):
+            raise ValueError("multi-modal encoder: every modality needs the same batch and one mask (or masks=None)")
+        if S > 64:      # (vct_attn_*: Lq, Lk <= 64 -- the encoder's self-attention and the decoder's cross-attention)
+            raise ValueError(f"multi-modal encoder: {S} memory rows (sum of T_i + 1 over the streams {Ts}); the attention kernels "
+                             "take at most 64")
+        self.p_drop = self.cfg["dropout"] if training else 0.0
+        b = self.buf((B, Ts))
+        self.cur, self.shape, self.mm_Ts = b, (B, S - 1), Ts
+        us = []
+        for i, f in enumerate(feats):
+            E = f.shape[2]
+            x_in = f.reshape(B * Ts[i], E)
+            if not x_in.is_contiguous():
+                x_in = x_in.contiguous()
+            if x_in.dtype != self.dt:
+                x_in = ops.cast(x_in, b.get(f"feats_c{i}", (B * Ts[i], E), self.dt))
+            b.t[f"x_in{i}"] = x_in
+            u = b.get(f"u{i}", (B * Ts[i], d), self.dt)
+            ops.gemm(x_in, self.W(f"unify.{i}.weight"), u, bias=self.F(f"unify.{i}.bias"))
+            us.append(u)
+        kp, mks = None, None
+        if masks is not None:
+            mks = [(m if m.is_contiguous() else m.contiguous()) for m in masks]
+            mks = [m.view(torch.uint8) if m.dtype == torch.bool else m for m in mks]
+            kp = b.get("mm_kpm", (B, S), torch.uint8)
+        temp, labels = self.mm_rows(Ts)
+        x = ops.mm_frontend_fwd(us, mks, temp, self.F("modal_emb.modal_emb.weight"), labels, b.get("x0", (B * S, d), self.dt), kp,
+                                B, Ts)
+        kpm = (kp, 0) if kp is not None else None     # the [B, S] mask, no shift: both attention paths read it as is
+        b.t["kpm_used"] = kpm
+        return self._stack_fwd(b, x, B, S, kpm)
+
+    def _stack_fwd(self, b, x, B, Te, kpm) -> torch.Tensor:
+        """The encoder stack on its input x [B*Te, d]: sample-stationary when _ss_ok allows it, else layer by layer."""
+        L = self.cfg["layers"]
+        if self._ss_ok(Te, 0, B):
             x, mem = self._stack_ss(b, [f"transformer_encoder.layers.{l}." for l in range(L)], [f"L{l}." for l in range(L)], x, B, Te,
                                     [ENC_SITE + 16 * l for l in range(L)], ln_tag="n2.", ln_name="norm2.",
                                     final="transformer_encoder.norm.", kpm=kpm)
@@ -905,6 +1024,20 @@ class EncoderEngine(_StackBase):
             x = self._ln_fwd(b, tag + "n2.", lp + "norm2.", f, x1, site + 4)
         b.t["x_last"] = x
         return self._ln_fwd(b, "nf.", "transformer_encoder.norm.", x, None, None)
+
+    def _frontend_bwd(self, dx):
+        """From the gradient dx [B*S, d] of the stack input: the front end's backward, then the unify weight gradients (and, with
+        n >= 2 modalities, the modal-embedding gradient, WRITTEN by vct_mm_frontend_bwd)."""
+        b, (B, T), d = self.cur, self.shape, self.cfg["d"]
+        if self.mm_Ts is None:
+            du = ops.enc_frontend_bwd(dx, b.get("du", (B * T, d), self.dt), B, T)
+            self.dw_gemm(du, b.t["x_in"], self.G("unify.0.weight"), bias_grad=self.G("unify.0.bias"))
+            return
+        Ts = self.mm_Ts
+        dus = [b.get(f"du{i}", (B * t, d), self.dt) for i, t in enumerate(Ts)]
+        ops.mm_frontend_bwd(dx, dus, self.G("modal_emb.modal_emb.weight"), self.mm_rows(Ts)[1], B, Ts)
+        for i, du in enumerate(dus):
+            self.dw_gemm(du, b.t[f"x_in{i}"], self.G(f"unify.{i}.weight"), bias_grad=self.G(f"unify.{i}.bias"))
 
     def ss_bwd_ok(self) -> bool:
         """The current shape's activation-gradient chain runs as one sample-stationary launch (csrc/vct_layer_ss_bwd.hip)."""
@@ -932,8 +1065,7 @@ class EncoderEngine(_StackBase):
                 if bucket_ready is not None and l > 0:
                     self.flush_ln_grads(b)
                     self.bucket_on_side(bucket_ready, "enc_layer", l)
-            du = ops.enc_frontend_bwd(dx, b.get("du", (B * T, self.cfg["d"]), self.dt), B, T)
-            self.dw_gemm(du, b.t["x_in"], self.G("unify.0.weight"), bias_grad=self.G("unify.0.bias"))
+            self._frontend_bwd(dx)
             self.flush_ln_grads(b)
             if join or bucket_ready is not None:
                 self.join_side()
@@ -963,8 +1095,7 @@ class EncoderEngine(_StackBase):
             if bucket_ready is not None and l > 0:
                 self.flush_ln_grads(b)
                 self.bucket_on_side(bucket_ready, "enc_layer", l)
-        du = ops.enc_frontend_bwd(dx, b.get("du", (B * T, self.cfg["d"]), self.dt), B, T)
-        self.dw_gemm(du, b.t["x_in"], self.G("unify.0.weight"), bias_grad=self.G("unify.0.bias"))
+        self._frontend_bwd(dx)
         self.flush_ln_grads(b)
         if bucket_ready is None and self.enc_dw_main >= 2 and getattr(self, "main_stream", None) is not None:
             self.flush_dw_across(self.main_stream)       # (A/B: the bottom layer's group too)

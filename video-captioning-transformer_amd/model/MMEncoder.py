@@ -1,13 +1,12 @@
-"""MultiModalEncoder -- drop-in for the reference's model/MMEncoder.py:205-276 (the shipped path:
-one modality, `temporal: "encoding"`, `aggregation: "avg"`, do_norm False), executed by
-hand-written gfx950 kernels (engine.EncoderEngine).  Same constructor signature, same forward
-signature and return tuple, same state_dict keys."""
+"""MultiModalEncoder -- drop-in for the reference's model/MMEncoder.py:205-276 (`temporal: "encoding"`, `aggregation: "avg"`,
+do_norm False; one or more modalities), executed by hand-written gfx950 kernels (engine.EncoderEngine).  Same constructor
+signature, same forward signature and return tuple, same state_dict keys."""
 from typing import List, Optional
 
 import torch
 import torch.nn as nn
 
-from ..engine import EncoderEngine, ParamSet
+from ..engine import EncoderEngine, ParamSet, memory_len
 from ._params import LinearParams, StackParams, sinusoid_table
 
 
@@ -19,14 +18,29 @@ class TemporalEncoding(nn.Module):
         self.register_buffer("pe", sinusoid_table(max_len, d_model, "encoder", device).unsqueeze(0))
 
 
-def grad_ready_order_encoder(prefix, n_layers):
+class ModalEmbedding(nn.Module):
+    """Holds `modal_emb.weight`: [2n, d] when modal_different (one row per modality and one per aggregation row), else [n, d];
+    nn.Embedding's N(0, 1) initialisation (model/MMEncoder.py:12-24).  The lookup runs in vct_mm_frontend_fwd."""
+
+    def __init__(self, num_modal, d_model=512, modal_different=False, device=None):
+        super().__init__()
+        self.num_modal, self.embed_size, self.modal_different = num_modal, d_model, modal_different
+        self.modal_emb = nn.Embedding(num_modal * 2 if modal_different else num_modal, d_model, device=device)
+
+
+def grad_ready_order_encoder(prefix, n_layers, n_modal: int = 1):
     names = [prefix + "transformer_encoder.norm.weight", prefix + "transformer_encoder.norm.bias"]
     for l in reversed(range(n_layers)):
         lp = f"{prefix}transformer_encoder.layers.{l}."
         names += [lp + k for k in ("norm2.weight", "norm2.bias", "linear2.weight", "linear2.bias", "linear1.weight",
                                    "linear1.bias", "norm1.weight", "norm1.bias", "self_attn.out_proj.weight",
                                    "self_attn.out_proj.bias", "self_attn.in_proj_weight", "self_attn.in_proj_bias")]
-    return names + [prefix + "unify.0.weight", prefix + "unify.0.bias"]
+    names += [prefix + "unify.0.weight", prefix + "unify.0.bias"]
+    if n_modal > 1:      # after unify.0: the last gradient bucket (MMT4Caption.grad_buckets)
+        for i in range(1, n_modal):
+            names += [f"{prefix}unify.{i}.weight", f"{prefix}unify.{i}.bias"]
+        names.append(prefix + "modal_emb.modal_emb.weight")
+    return names
 
 
 class _EncoderFn(torch.autograd.Function):
@@ -35,8 +49,8 @@ class _EncoderFn(torch.autograd.Function):
         eng = mod._engine()
         mem = eng.forward(feats, mask, mod.training)
         ctx.mod = mod
-        B, T = feats.shape[0], feats.shape[1]
-        return mem.view(B, T + 1, -1)
+        B = feats[0].shape[0] if isinstance(feats, (list, tuple)) else feats.shape[0]
+        return mem.view(B, memory_len(feats), -1)
 
     @staticmethod
     def backward(ctx, dmem):
@@ -53,17 +67,19 @@ class MultiModalEncoder(nn.Module):
                  modal_different: bool = True, temporal_type: str = "embedding", do_norm: bool = False,
                  device=torch.device("cuda"), compute_dtype: torch.dtype = torch.bfloat16):
         super().__init__()
-        if len(d_feats) != 1:
-            raise NotImplementedError("multi-modal input (ModalEmbedding) is outside the accelerated caption path")
+        if len(d_feats) < 1:
+            raise ValueError("MultiModalEncoder needs at least one feature stream")
         if global_type != "avg" or temporal_type != "encoding" or do_norm:
             raise NotImplementedError("accelerated path = aggregation 'avg', temporal 'encoding', do_norm False "
                                       "(the shipped configs); other encoder variants are out of scope")
-        self.device, self.num_modal, self.do_norm = device, 1, do_norm
+        self.device, self.num_modal, self.do_norm = device, len(d_feats), do_norm
         self.cfg = dict(d=d_model, nhead=nhead, ff=dim_feedforward, layers=num_encoder_layers, dropout=float(dropout),
-                        activation=activation)
+                        activation=activation, n_modal=len(d_feats), modal_different=bool(modal_different))
         self.compute_dtype = compute_dtype
-        self.unify = nn.ModuleList([LinearParams(d_feats[0], d_model, device)])
+        self.unify = nn.ModuleList([LinearParams(e, d_model, device) for e in d_feats])
         self.temp_emb = TemporalEncoding(d_model, device=device)
+        if self.num_modal > 1:        # (a single modality has no modal embedding, MMEncoder.py:232)
+            self.modal_emb = ModalEmbedding(self.num_modal, d_model, modal_different, device)
         self.transformer_encoder = StackParams(d_model, dim_feedforward, num_encoder_layers, False, device)
         self._ps: Optional[ParamSet] = None   # set by the owner (MMT4Caption) or lazily for standalone use
         self._prefix = ""
@@ -80,7 +96,7 @@ class MultiModalEncoder(nn.Module):
                 self._rebuild()
         elif self._ps is None or not self._ps.intact():
             named = dict(self.named_parameters())
-            order = grad_ready_order_encoder("", self.cfg["layers"])
+            order = grad_ready_order_encoder("", self.cfg["layers"], self.num_modal)
             dev = next(self.parameters()).device
             self._ps = ParamSet([(n, named[n]) for n in order], dev, self.compute_dtype)
             self._prefix, self._eng = "", None
@@ -91,15 +107,24 @@ class MultiModalEncoder(nn.Module):
 
     # ---- reference API ---------------------------------------------------------------------------
     def forward(self, srcs: List[torch.Tensor], src_padding_masks: Optional[List[torch.Tensor]]):
-        """srcs: [Tensor[B,T,E]] fp32; src_padding_masks: [Tensor[B,T] bool] (True = padded) or None.
-        Returns (memory[B,T+1,d], global_masks[B,T+1] or None, memory[:,0]) like MMEncoder.py:276."""
-        feats = srcs[0]
-        mask = src_padding_masks[0] if src_padding_masks is not None else None
+        """srcs: one Tensor[B,T_i,E_i] fp32 per modality; src_padding_masks: one Tensor[B,T_i] bool (True = padded) per modality,
+        or None.  Returns (memory[B,S,d], global_masks[B,S] or None, memory[:,0]) like MMEncoder.py:276, S = sum_i (T_i + 1)."""
+        if len(srcs) != self.num_modal:
+            raise ValueError(f"expected {self.num_modal} feature streams, got {len(srcs)}")
+        if self.num_modal == 1:
+            feats = srcs[0]
+            mask = src_padding_masks[0] if src_padding_masks is not None else None
+        else:
+            feats = list(srcs)
+            mask = list(src_padding_masks) if src_padding_masks is not None else None
         eng = self._engine()
         eng.ps.refresh_shadow()
         mem = _EncoderFn.apply(self, feats, mask, *[self._ps.params[n] for n in self._ps.names])
         mem = mem.float() if mem.dtype != torch.float32 else mem.clone()
         gmask = None
-        if mask is not None:
-            gmask = torch.cat([torch.zeros(mask.shape[0], 1, dtype=torch.bool, device=mask.device), mask], 1)
+        if src_padding_masks is not None:
+            parts = []
+            for m in src_padding_masks:
+                parts += [torch.zeros(m.shape[0], 1, dtype=torch.bool, device=m.device), m]
+            gmask = torch.cat(parts, 1)
         return mem, gmask, mem[:, 0]

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..engine import ParamSet
+from ..engine import ParamSet, first_input, memory_len
 from .CapDecoder import CapDecoder, grad_ready_order_decoder
 from .CapPreprocessor import CapPreprocessor
 from .Matching import Matching, TextEncoder
@@ -86,7 +86,7 @@ class MMT4Caption(nn.Module):
     def _build_flat(self):
         named = dict(self.named_parameters())
         order = (grad_ready_order_decoder("cap_decoder.", self.cap_decoder.cfg["layers"]) +
-                 grad_ready_order_encoder("video_encoder.", self.video_encoder.cfg["layers"]))
+                 grad_ready_order_encoder("video_encoder.", self.video_encoder.cfg["layers"], self.video_encoder.num_modal))
         order += [n for n in named if n not in set(order)]   # matching.* (not on the caption path)
         dev = named[order[0]].device
         self._ps = ParamSet([(n, named[n]) for n in order], dev, self.compute_dtype, no_shadow=("cap_decoder.tgt_to_emb.weight",))
@@ -153,16 +153,18 @@ class MMT4Caption(nn.Module):
 
     # ---- engine-level forward/backward (no autograd) ------------------------------------------------
     def _forward_loss(self, feats, mask, ids, training, want_logits=False):
+        """feats / mask: one tensor (one modality) or one tensor per modality (mask: a list or None)."""
         if not self._ps.intact():
             self._build_flat()
         self._ps.refresh_shadow()
         enc, dec = self.video_encoder._engine(), self.cap_decoder._engine()
+        B, Te = first_input(feats).shape[0], memory_len(feats)      # Te: the encoder's memory rows per sample
         ops.tap("layers_fwd", 0)      # bench.py north_star bracket: input cast .. decoder final LayerNorm (main stream)
         if self.overlap_dec_prefix and dec.dev.type == "cuda" and dec.overlap_dw:
             # token embedding + the decoder's bottom self-attention block do not need the encoder: side stream, beside it
-            dec.forward_prefix(feats.shape[0], feats.shape[1] + 1, ids, training)
+            dec.forward_prefix(B, Te, ids, training)
         mem = enc.forward(feats, mask, training)
-        loss, logits = dec.forward(mem, feats.shape[0], feats.shape[1] + 1, ids, training, want_logits=want_logits)
+        loss, logits = dec.forward(mem, B, Te, ids, training, want_logits=want_logits)
         return loss, logits
 
     @property
@@ -228,11 +230,11 @@ class MMT4Caption(nn.Module):
             dmem = dec.backward(hook)
             enc.backward(dmem, hook)
 
-    def train_step_kernels(self, feats: torch.Tensor, mask: Optional[torch.Tensor], ids: torch.Tensor,
-                           bucket_ready=None, defer_join: bool = False) -> torch.Tensor:
+    def train_step_kernels(self, feats, mask, ids: torch.Tensor, bucket_ready=None, defer_join: bool = False) -> torch.Tensor:
         """Fast path used by the trainer and bench: forward + backward as one static kernel schedule
         (hipGraph-capturable, no autograd tape).  Gradients are WRITTEN (not accumulated) into the flat
-        gradient buffer, whose views are installed as `.grad`.  Returns the loss tensor [1]."""
+        gradient buffer, whose views are installed as `.grad`.  Returns the loss tensor [1].
+        feats / mask: a tensor (one modality) or a list with one tensor per modality (mask: a list or None)."""
         loss, _ = self._forward_loss(feats, mask, ids, self.training)
         self._backward(bucket_ready, join=not defer_join)     # defer_join: the caller calls join_backward() itself
         opt = self._ps.dw_adam                                # the optimizer epilogue consumed the weight gradients unless told to store them
@@ -240,6 +242,20 @@ class MMT4Caption(nn.Module):
         return loss
 
     # ---- reference API -----------------------------------------------------------------------------
+    def _video_inputs(self, video_feats, video_masks):
+        """The reference's per-modality lists -> what the engines take: the tensor itself for one modality (a bare tensor is
+        accepted too), the list for several."""
+        n = self.video_encoder.num_modal
+        if isinstance(video_feats, torch.Tensor):
+            if n > 1:
+                raise ValueError(f"the model has {n} feature streams: pass one tensor per stream, not a single tensor")
+            return video_feats, (video_masks[0] if isinstance(video_masks, (list, tuple)) else video_masks)
+        if n == 1:
+            return video_feats[0], (video_masks[0] if video_masks is not None else None)
+        if len(video_feats) != n or (video_masks is not None and len(video_masks) != n):
+            raise ValueError(f"expected {n} feature streams (and as many masks, or None), got {len(video_feats)}")
+        return list(video_feats), (list(video_masks) if video_masks is not None else None)
+
     def forward(self, video_feats: List[torch.Tensor], video_masks: List[torch.Tensor], captions):
         if self.f_type == "caption":
             return self.caption_forward(video_feats, video_masks, captions)
@@ -249,8 +265,7 @@ class MMT4Caption(nn.Module):
 
     def caption_forward(self, video_feats, video_masks, captions):
         text_ts, _text_mask_ts = self.cap_preprocessor(captions)
-        mask = video_masks[0] if video_masks is not None else None
-        feats = video_feats[0]
+        feats, mask = self._video_inputs(video_feats, video_masks)
         if not torch.is_grad_enabled():
             return self._forward_loss(feats, mask, text_ts, self.training)[0][0].clone()
         return _CaptionFn.apply(self, feats, mask, text_ts, *[self._ps.params[n] for n in self._ps.names]).clone().reshape(())
@@ -283,10 +298,10 @@ class MMT4Caption(nn.Module):
         self.eval()
         try:
             from .. import decode
-            mask = video_masks[0] if video_masks is not None else None
+            feats, mask = self._video_inputs(video_feat, video_masks)
             if kv_cache:
-                return decode.greedy_decode_ids(self, video_feat[0], mask, max_len, use_graphs=use_graphs)
-            return decode.greedy_decode_ids_reference_algorithm(self, video_feat[0], mask, max_len)
+                return decode.greedy_decode_ids(self, feats, mask, max_len, use_graphs=use_graphs)
+            return decode.greedy_decode_ids_reference_algorithm(self, feats, mask, max_len)
         finally:
             self.train(was_training)
 
@@ -306,11 +321,11 @@ class MMT4Caption(nn.Module):
         self.eval()
         try:
             from .. import decode
-            mask = video_masks[0] if video_masks is not None else None
+            feats, mask = self._video_inputs(video_feat, video_masks)
             if kv_cache:
-                return decode.beam_decode_ids(self, video_feat[0], mask, beam_size, max_len, length_penalty,
+                return decode.beam_decode_ids(self, feats, mask, beam_size, max_len, length_penalty,
                                               use_graphs=use_graphs, return_all=return_all)
-            return decode.beam_decode_ids_reference_algorithm(self, video_feat[0], mask, beam_size, max_len, length_penalty,
+            return decode.beam_decode_ids_reference_algorithm(self, feats, mask, beam_size, max_len, length_penalty,
                                                               return_all=return_all)[0]
         finally:
             self.train(was_training)

@@ -368,6 +368,42 @@ def enc_frontend_bwd(dz, du, B, T):
     return du
 
 
+def _mm_desc(dtype, B, d, Ts, labels, n_labels):
+    if not 2 <= len(Ts) <= L.MM_MAX_MODAL:
+        raise ValueError(f"multi-modal front end: 2..{L.MM_MAX_MODAL} modalities, got {len(Ts)}")
+    if labels.dtype != torch.int32 or labels.numel() != sum(t + 1 for t in Ts):
+        raise ValueError("multi-modal front end: labels must be int32 [sum(T_i + 1)]")
+    desc = L.MmFrontendDesc()
+    desc.dtype, desc.n, desc.B, desc.d, desc.n_labels = L.dtype_code(dtype), len(Ts), B, d, n_labels
+    for i, t in enumerate(Ts):
+        desc.T[i] = int(t)
+    desc.labels = labels.data_ptr()
+    return desc
+
+
+def mm_frontend_fwd(us, masks, temp, modal_w, labels, x0, key_pad, B, Ts):
+    """Multi-modal front end (include/vct_hip.h, vct_mm_frontend_fwd): us[i] [B*T_i, d] unify outputs, masks[i] uint8 [B, T_i] or
+    None, temp fp32 [S, d], modal_w fp32 [n_labels, d], labels int32 [S] -> x0 [B*S, d], key_pad uint8 [B, S] (or None)."""
+    d = x0.shape[-1]
+    desc = _mm_desc(x0.dtype, B, d, Ts, labels, modal_w.shape[0])
+    for i, u in enumerate(us):
+        desc.u[i] = u.data_ptr()
+        desc.mask[i] = L.ptr(masks[i]) if masks is not None else 0
+    desc.temp, desc.modal_w, desc.x0, desc.key_pad = temp.data_ptr(), modal_w.data_ptr(), x0.data_ptr(), L.ptr(key_pad)
+    L.check(L.load().vct_mm_frontend_fwd(L.C.byref(desc), L.stream_ptr()), "vct_mm_frontend_fwd")
+    return x0
+
+
+def mm_frontend_bwd(dx, dus, d_modal, labels, B, Ts):
+    """Backward of mm_frontend_fwd: dus[i] [B*T_i, d] <- dx [B*S, d]; d_modal fp32 [n_labels, d] is WRITTEN."""
+    desc = _mm_desc(dx.dtype, B, dx.shape[-1], Ts, labels, d_modal.shape[0])
+    for i, du in enumerate(dus):
+        desc.du[i] = du.data_ptr()
+    desc.dx, desc.d_modal = dx.data_ptr(), d_modal.data_ptr()
+    L.check(L.load().vct_mm_frontend_bwd(L.C.byref(desc), L.stream_ptr()), "vct_mm_frontend_bwd")
+    return dus
+
+
 def embed_fwd(ids, S, table, pos, x, dropout: Drop = None):
     """ids: int64 [B, S_total] (row stride = ids.stride(0)); uses the first S columns of each row."""
     B = ids.shape[0]

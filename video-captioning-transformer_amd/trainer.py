@@ -12,6 +12,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
+from .engine import first_input, stage_inputs, static_inputs
 from .utils import capture_graph
 
 
@@ -537,7 +538,7 @@ class CaptionTrainer:
             else:
                 self.ex.finish()
                 self.opt.step()
-        elif fused and self.overlap_adam and feats.is_cuda:
+        elif fused and self.overlap_adam and first_input(feats).is_cuda:
             # single GPU: Adam on each gradient bucket the moment backward completes it, on the side stream, so the
             # 1.4 GB optimizer pass hides under the rest of backward instead of trailing it
             buckets = m.grad_buckets()
@@ -555,7 +556,7 @@ class CaptionTrainer:
             if ctx.side is not None:
                 ops.stream_wait(None, ctx.side)
             self.opt.finish_ranges()
-        elif fused and feats.is_cuda and m.overlap_enc_bwd and not self.adam_after_backward:
+        elif fused and first_input(feats).is_cuda and m.overlap_enc_bwd and not self.adam_after_backward:
             # the encoder backward is still running on the side stream when the decoder's tail is done: Adam on everything
             # but the encoder (86 % of the parameters at cfg-B) fills that gap on the main stream, the rest follows the join
             loss = m.train_step_kernels(feats, mask, ids, defer_join=True)
@@ -578,7 +579,7 @@ class CaptionTrainer:
         else:
             loss = m.train_step_kernels(feats, mask, ids)
             self.opt.step()
-        if self.warm_streams and feats.is_cuda:
+        if self.warm_streams and first_input(feats).is_cuda:
             # the next step begins with the two sample-stationary stack launches, which stream these packed weights chunk by chunk with
             # two chunks of prefetch: behind the optimizer's passes (1.4 GB of traffic through the memory-side cache) every chunk is an
             # HBM miss
@@ -607,32 +608,36 @@ class CaptionTrainer:
             st = self._static = {}
         s = st.get(key)
         if s is None:
-            s = st[key] = (feats.clone(), None if mask is None else mask.clone(), ids.clone())
+            s = st[key] = (static_inputs(feats), static_inputs(mask), ids.clone())
         else:
             # a caller that already works in the static buffers (adopt_inputs) skips the staging copies: three small device copies
             # and the launch gaps around them are ~35 us at the head of a 2.4 ms step
-            if s[0].data_ptr() != feats.data_ptr():
-                s[0].copy_(feats, non_blocking=True)
-            if mask is not None and s[1].data_ptr() != mask.data_ptr():
-                s[1].copy_(mask, non_blocking=True)
+            stage_inputs(s[0], feats, non_blocking=True)
+            if mask is not None:
+                stage_inputs(s[1], mask, non_blocking=True)
             if s[2].data_ptr() != ids.data_ptr():
                 s[2].copy_(ids, non_blocking=True)
         return s
 
     def _input_key(self, feats, mask, ids):
+        if isinstance(feats, (list, tuple)):       # one tensor per modality
+            return (tuple((tuple(f.shape), f.dtype) for f in feats), None if mask is None else tuple(tuple(m.shape) for m in mask),
+                    tuple(ids.shape), self.model.training)
         return (tuple(feats.shape), feats.dtype, None if mask is None else tuple(mask.shape), tuple(ids.shape), self.model.training)
 
-    def adopt_inputs(self, feats: torch.Tensor, mask: Optional[torch.Tensor], ids: torch.Tensor):
+    def adopt_inputs(self, feats, mask, ids: torch.Tensor):
         """The trainer's own static input buffers for this shape, initialised with the given batch.  Recorded launch lists and
         captured graphs read their inputs from these buffers, so step() normally copies every batch into them; a producer that
         writes its batches INTO them (a device-side loader, a benchmark with resident data) and passes them to step() has no copy
-        left.  Returns (feats, mask, ids) views of the buffers; without a recording executor the inputs are returned unchanged."""
+        left.  Returns (feats, mask, ids) views of the buffers; without a recording executor the inputs are returned unchanged.
+        feats / mask: a tensor, or one tensor per modality (mask: that list or None)."""
         if not (self.use_graph or self.use_list):
             return feats, mask, ids
         return self._static_inputs(self._input_key(feats, mask, ids), feats, mask, ids)
 
-    def step(self, feats: torch.Tensor, mask: Optional[torch.Tensor], ids: torch.Tensor) -> torch.Tensor:
-        """Returns this rank's loss as a device tensor [1] (no host sync)."""
+    def step(self, feats, mask, ids: torch.Tensor) -> torch.Tensor:
+        """Returns this rank's loss as a device tensor [1] (no host sync).  feats / mask: a tensor (one modality), or one tensor
+        per modality (mask: that list or None)."""
         if isinstance(self.opt, FusedAdam):
             self.opt.sync_hyper()
         if not (self.use_graph or self.use_list):
@@ -700,9 +705,14 @@ def train_epoch(model, optimizer, dataloader, mode: str = "caption", exchange: O
     dev = model.flat_params.device
     total = torch.zeros(1, device=dev)
     n = 0
+    n_modal = model.video_encoder.num_modal
     for v_feats, v_masks, captions, _vids in dataloader:
-        feats = v_feats[0].to(dev, non_blocking=True)
-        mask = v_masks[0].to(dev, non_blocking=True) if v_masks is not None else None
+        if n_modal > 1:      # every modality (MMEncoder.forward takes the lists)
+            feats = [f.to(dev, non_blocking=True) for f in v_feats]
+            mask = [m.to(dev, non_blocking=True) for m in v_masks] if v_masks is not None else None
+        else:
+            feats = v_feats[0].to(dev, non_blocking=True)
+            mask = v_masks[0].to(dev, non_blocking=True) if v_masks is not None else None
         ids, _ = model.cap_preprocessor(captions)
         total += trainer.step(feats, mask, ids)
         n += 1
