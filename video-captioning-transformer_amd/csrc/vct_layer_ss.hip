@@ -3,7 +3,7 @@
 //     ONE launch = ONE whole nn.TransformerEncoderLayer / nn.TransformerDecoderLayer (+ optionally the stack-final LayerNorm)
 //     ONE 512-thread workgroup = ONE sample: its <= 32 token rows stay in LDS from the layer input to the layer output
 //
-// replaces, per layer, the 9-14 launches of the unfused schedule (engine.py: _attn_ln_fwd / _ffn_fwd / _ln_fwd): in-projection GEMM(s),
+// replaces, per layer, the 9-14 launches of the unfused schedule (engine/stack.py: _attn_ln_fwd / _ffn_fwd / _ln_fwd): in-projection GEMM(s),
 // attention core, out_proj GEMM, add + LayerNorm, cross-attention likewise, linear1 (+GELU, dropout), linear2, add + LayerNorm --
 // i.e. torch nn/modules/transformer.py:951-982 (encoder layer) and :1143-1199 (decoder layer) as built at MMEncoder.py:236-238 and
 // CapDecoder.py:18-20, with nn.MultiheadAttention = torch nn/functional.py:6206-6640.

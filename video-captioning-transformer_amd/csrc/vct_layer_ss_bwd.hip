@@ -3,7 +3,7 @@
 //     ONE launch = the activation-gradient chain of a whole nn.TransformerEncoder stack, top layer first (+ the stack-final LayerNorm)
 //     ONE 512-thread workgroup = ONE sample: the gradient rows stay in registers / LDS from the stack output to the stack input
 //
-// replaces, per encoder layer, the 7 launches of the unfused dX chain (engine.py: _ln_bwd / _ffn_bwd / _attn_block_bwd): LayerNorm
+// replaces, per encoder layer, the 7 launches of the unfused dX chain (engine/stack.py: _ln_bwd / _ffn_bwd / _attn_block_bwd): LayerNorm
 // backward, the two feed-forward input-gradient GEMMs (GELU' and dropout in the first one's epilogue), LayerNorm backward, the
 // out_proj input-gradient GEMM, the attention backward core and the in_proj input-gradient GEMM -- the autograd nodes of torch
 // nn/modules/transformer.py:951-982 as built at MMEncoder.py:236-238.  The WEIGHT gradients are not sample-local (their K dimension is

@@ -1,5 +1,5 @@
 """CapDecoder -- drop-in for the reference's model/CapDecoder.py:11-79, executed by hand-written
-gfx950 kernels (engine.DecoderEngine).  Same constructor / forward / decode_word signatures, same
+gfx950 kernels (engine/decoder.py: DecoderEngine).  Same constructor / forward / decode_word signatures, same
 state_dict keys (decoder.layers.N.*, decoder.norm, generator, tgt_to_emb, positional_encoding)."""
 from typing import Optional
 

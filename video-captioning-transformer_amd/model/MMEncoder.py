@@ -1,5 +1,5 @@
 """MultiModalEncoder -- drop-in for the reference's model/MMEncoder.py:205-276 (`temporal: "encoding"`, `aggregation: "avg"`,
-do_norm False; one or more modalities), executed by hand-written gfx950 kernels (engine.EncoderEngine).  Same constructor
+do_norm False; one or more modalities), executed by hand-written gfx950 kernels (engine/encoder.py: EncoderEngine).  Same constructor
 signature, same forward signature and return tuple, same state_dict keys."""
 from typing import List, Optional
 

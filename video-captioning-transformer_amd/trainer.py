@@ -468,7 +468,7 @@ class CaptionTrainer:
       * use_graph=True: the step is captured into a hipGraph (bitwise equal, but replay serialises the two streams).
     Inputs are copied into static buffers; the dropout seed, the Adam step counter and the Adam hyper-parameters live
     in device memory, so every replay sees fresh values.  Recordings are dropped when an activation buffer of THIS model had
-    to grow (engine.StepContext.generation), because they bake device pointers."""
+    to grow (engine/params.py: StepContext.generation), because they bake device pointers."""
 
     def __init__(self, model, optimizer, exchange: Optional[GradExchange] = None, use_graph: bool = False,
                  launch_list: Optional[bool] = None, keep_weight_grads: Optional[bool] = None):
