@@ -154,8 +154,9 @@ def test_cfgB_full_batch_256_vs_oracle(dtype, tg):
             # the packed weight streams of the two stacks, maintained by the optimizer epilogues of the weight-gradient GEMMs at the
             # benchmark shape == a fresh pack of the shadow, bit for bit
             from vct_amd import ops
-            for key, (stream, _firsts, subs) in mm._ps.packed.items():
-                fresh = ops.ss_pack([blk for sub in subs for blk in sub[2]], stream.clone())
+            for key, packed in mm._ps.packed.items():
+                stream = packed.t
+                fresh = ops.ss_pack([blk for part in packed.parts for blk in part.blocks], stream.clone())
                 torch.cuda.synchronize()
                 assert torch.equal(fresh.view(torch.int16), stream.view(torch.int16)), key
         assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])

@@ -328,7 +328,7 @@ def test_vocabulary_dx_through_the_maintained_transposed_shadow(monkeypatch):
         ps = m._ps
         name = "cap_decoder.generator.weight"
         assert name in ps.transposed
-        t = ps.transposed[name][0]
+        t = ps.transposed[name].t
         w = ps.c[name]
         assert torch.equal(t[:, :w.shape[0]], w.t())
         l1 = torch.cat(losses)
@@ -502,6 +502,6 @@ def test_decode_after_training_steps_uses_the_current_weights():
     ys_ref = ref.greedy_decode_ids([feats], None, max_len=8)
     assert torch.equal(ys1, ys_ref)
     for name, ent in m._ps.transposed.items():
-        if not ent[3]:
+        if not ent.eager:
             w = m._ps.c[name]
-            assert torch.equal(ent[0][:, :w.shape[0]], w.t()), name
+            assert torch.equal(ent.t[:, :w.shape[0]], w.t()), name

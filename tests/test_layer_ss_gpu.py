@@ -208,8 +208,9 @@ def test_packed_stream_follows_the_weights():
             if fused:      # the packed streams the optimizer's pass maintains == a fresh vct_ss_pack of the current shadow, bit for bit
                 from vct_amd import ops
                 assert m._ps.packed
-                for key, (stream, _firsts, subs) in m._ps.packed.items():
-                    fresh = ops.ss_pack([blk for sub in subs for blk in sub[2]], torch.zeros_like(stream))
+                for key, packed in m._ps.packed.items():
+                    stream = packed.t
+                    fresh = ops.ss_pack([blk for part in packed.parts for blk in part.blocks], torch.zeros_like(stream))
                     torch.cuda.synchronize()
                     assert torch.equal(fresh.view(torch.int16), stream.view(torch.int16)), key
     finally:
@@ -251,8 +252,9 @@ def test_packed_stream_created_after_a_recording_is_kept_current():
                     torch.cuda.synchronize()
                     if k >= 1:
                         assert any("decoder" in key for key in m._ps.packed), list(m._ps.packed)
-                    for key, (stream, _firsts, subs) in m._ps.packed.items():
-                        fresh = ops.ss_pack([blk for sub in subs for blk in sub[2]], stream.clone())
+                    for key, packed in m._ps.packed.items():
+                        stream = packed.t
+                        fresh = ops.ss_pack([blk for part in packed.parts for blk in part.blocks], stream.clone())
                         torch.cuda.synchronize()
                         assert torch.equal(fresh.view(torch.int16), stream.view(torch.int16)), (k, key)
             out[fused] = losses

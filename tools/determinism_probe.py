@@ -34,7 +34,7 @@ for rep in range(int(os.environ.get("REPS", "4"))):
         for s in range(nsteps):
             losses.append(tr.step(feats, mask, idt).clone())
             grads.append(mm.flat_grads.clone()); pars.append(mm.flat_params.clone()); shads.append(mm._ps.cflat.clone())
-            wt = mm._ps.transposed.get('cap_decoder.generator.weight'); shads.append(wt[0].clone() if wt else torch.zeros(1))
+            wt = mm._ps.transposed.get('cap_decoder.generator.weight'); shads.append(wt.t.clone() if wt else torch.zeros(1))
         torch.cuda.synchronize()
         outs.append((torch.cat(losses), grads, mm.flat_params.clone(), mm._ps, pars, shads))
     (la, ga, pa, ps, para, sha), (lb, gb, pb, _, parb, shb) = outs

@@ -81,7 +81,7 @@ def _run_session(model, st, feats, mask, max_len, use_graphs, sync_every, lookah
     model._ps.refresh_shadow()
     model._ps.refresh_lazy_transposed()
     enc = model.video_encoder._engine()
-    stamp = model._ps._stamp
+    stamp = model._ps.stamp
     if st.__dict__.get("weights_stamp") != stamp:      # graphs bake weight pointers only, but keep it simple and safe
         st.weights_stamp = stamp
     on_gpu = _first(feats).device.type == "cuda"

@@ -1,10 +1,61 @@
 """The parameter set of one model (fp32 masters, gradients, compute-dtype shadow, transposed / packed weight copies, Adam tables)
 and the named static buffers the engines work in."""
-from typing import List
+import bisect
+from dataclasses import dataclass
+from typing import Dict, List, Optional
 
 import torch
 
 from .. import ops
+
+
+# The derived weight copies a step keeps in sync with the compute-dtype shadow.  Plain records: ParamSet's methods hold the behaviour.
+
+@dataclass(eq=False, slots=True)
+class TransposedCopy:
+    """A [cols, ld] transposed copy of one weight matrix (ParamSet.transposed[name])."""
+    t: torch.Tensor
+    start: int          # flat elements [start, end) of the weight
+    end: int
+    eager: bool         # rewritten whenever the shadow of the weight is; else on demand (want_transposed)
+    version: int        # ParamSet.version the copy was made at (-1: never written)
+
+
+@dataclass(eq=False, slots=True)
+class PackedPart:
+    """One part (a layer, or the unify weight in front of an encoder stack) of a packed stream."""
+    start: int          # flat elements [start, end) that hold the part's weights
+    end: int
+    blocks: list        # (2-D shadow view, nchunks, first chunk in the stream[, transposed]): what ops.ss_pack takes
+    dirty: bool         # the shadow moved on and nobody re-packed the part yet
+
+
+@dataclass(eq=False, slots=True)
+class PackedStream:
+    """The weights of a whole stack in the order the sample-stationary kernel consumes them (ParamSet.packed[key])."""
+    t: torch.Tensor
+    firsts: list        # first chunk of every part
+    parts: List[PackedPart]
+
+
+@dataclass(eq=False, slots=True)
+class AdamPackSeg:
+    """One weight whose packed copy the optimizer's pass writes itself (a row of the device table of vct_adam_pack_seg)."""
+    begin: int          # flat elements [begin, end) of the weight
+    end: int
+    K: int
+    mode: int           # 0: blocks of 512 rows, 1: slices of 512 columns
+    chunk0: list        # first chunk of each of the (up to) 4 blocks, -1: not packed
+    stream: int         # device pointer of the packed stream
+
+
+@dataclass(eq=False, slots=True)
+class AdamPackEntry:
+    """What ParamSet.adam_pack_table caches per (range, set of streams)."""
+    table: Optional[torch.Tensor]
+    nseg: int
+    parts: List[PackedPart]
+    segs: Dict[str, AdamPackSeg]
 
 
 class StepContext:
@@ -53,13 +104,13 @@ class ParamSet:
             self.c = {n: self.cflat[self.offsets[n]:self.offsets[n] + p.numel()].view(p.shape) for n, p in named}
         self._stamp = None
         self.version = 0        # bumped whenever the shadow is (or may have been) rewritten: lazy transposed copies key on it
-        # transposed copies of individual weight matrices in the compute dtype (name -> (tensor [cols, ld], start, end)): kept in
+        # transposed copies of individual weight matrices in the compute dtype (name -> TransposedCopy): kept in
         # step with the shadow by refresh_shadow / cast_range / FusedAdam.step_range (refresh_transposed)
-        self.transposed = {}
-        # STREAM-ORDER packed copies of whole stacks (key -> [tensor, chunks per layer, [[start, end, blocks, dirty] per layer]]): the operand of the
+        self.transposed: Dict[str, TransposedCopy] = {}
+        # STREAM-ORDER packed copies of whole stacks (key -> PackedStream): the operand of the
         # sample-stationary layer kernels (ops.layer_ss_fwd), kept in step with the shadow exactly like the eager transposed copies
-        self.packed = {}
-        self._adam_pack = {}
+        self.packed: Dict[str, PackedStream] = {}
+        self._adam_pack: Dict[tuple, AdamPackEntry] = {}
         # the optimizer that steps weight matrices INSIDE their weight-gradient GEMMs (trainer.FusedAdam.enable_dw_fusion; None: nobody
         # does): _StackBase.dw_gemm asks it for the epilogue descriptor of every gradient view it is about to produce
         self.dw_adam = None
@@ -85,20 +136,42 @@ class ParamSet:
                 return False
         return True
 
+    def _masters_stamp(self) -> int:
+        return sum(p._version for p in self.params.values())
+
+    @property
+    def stamp(self):
+        """Changes whenever the masters were written since the shadow last followed them (None: never cast)."""
+        return self._stamp
+
     def refresh_shadow(self, force=False):
         """bf16 shadow <- fp32 masters (one cast kernel per contiguous range)."""
         if self.compute_dtype == torch.float32:
             return
         stamp = None
         if not force:
-            stamp = sum(p._version for p in self.params.values())
+            stamp = self._masters_stamp()
             if stamp == self._stamp:
                 return
         for a, b in self.cast_ranges:
             ops.cast(self.flat[a:b], self.cflat[a:b])
         self.version += 1
         self.refresh_transposed(0, self.total)
-        self._stamp = stamp if stamp is not None else sum(p._version for p in self.params.values())
+        self._stamp = stamp if stamp is not None else self._masters_stamp()
+
+    def masters_written(self):
+        """A torch optimizer wrote the fp32 masters: re-cast the shadow and take the new stamp (fp32 mode: the stamp only)."""
+        self.refresh_shadow(force=True)
+        self._stamp = self._masters_stamp()
+
+    def optimizer_stepped(self):
+        """The fused optimizer stepped the masters and rewrote the shadow (and the eager copies) itself."""
+        self.version += 1
+        self._stamp = self._masters_stamp()
+
+    def shadow_replayed(self):
+        """A replayed recording of a step rewrote the shadow (lazy transposed copies key on `version`)."""
+        self.version += 1
 
     def cast_range(self, a: int, b: int):
         """bf16 shadow <- fp32 masters for flat elements [a, b) (minus the tensors that have no shadow)."""
@@ -123,15 +196,15 @@ class ParamSet:
             rows, cols = w.shape
             t = torch.zeros(cols, (rows + 31) // 32 * 32, dtype=w.dtype, device=w.device)
             a = self.offsets[name]
-            ent = self.transposed[name] = [t, a, a + w.numel(), bool(eager), -1]
-        was_lazy = not ent[3]
+            ent = self.transposed[name] = TransposedCopy(t, a, a + w.numel(), bool(eager), -1)
+        was_lazy = not ent.eager
         if eager:
-            ent[3] = True
-        if ent[4] != self.version:
-            if ent[4] < 0 or was_lazy:                # new, or a (so far) lazy copy that is out of date
-                ops.transpose(self.c[name], ent[0])
-            ent[4] = self.version
-        return ent[0]
+            ent.eager = True
+        if ent.version != self.version:
+            if ent.version < 0 or was_lazy:           # new, or a (so far) lazy copy that is out of date
+                ops.transpose(self.c[name], ent.t)
+            ent.version = self.version
+        return ent.t
 
     def want_packed(self, key: str, layers):
         """(stream, [first chunk of every part]): the weights of a whole Transformer STACK packed, part after part, in the order the
@@ -153,54 +226,54 @@ class ParamSet:
             for names, blocks in parts:
                 a = min(self.offsets[n] for n in names)
                 b = max(self.offsets[n] + self.params[n].numel() for n in names)
-                subs.append([a, b, blocks, True])
-            ent = self.packed[key] = [t, firsts, subs]
+                subs.append(PackedPart(a, b, blocks, True))
+            ent = self.packed[key] = PackedStream(t, firsts, subs)
             # a NEW stream changes what a step launches (the optimizer's pass / the pack launch behind it now also writes this
             # stream): recordings made before it existed would replay without refreshing it -> drop them (ctx.generation is what
             # CaptionTrainer keys its launch lists / graphs on)
             self.ctx.generation += 1
         todo = []
-        for sub in ent[2]:
-            if sub[3]:
-                todo += sub[2]
-                sub[3] = False
+        for part in ent.parts:
+            if part.dirty:
+                todo += part.blocks
+                part.dirty = False
         if todo:
-            ops.ss_pack(todo, ent[0])
-        return ent[0], ent[1]
+            ops.ss_pack(todo, ent.t)
+        return ent.t, ent.firsts
 
     def refresh_lazy_transposed(self):
         """Bring every on-demand transposed copy up to date (decode entry points call this before replaying captured steps,
         which bake the copies' addresses but cannot notice that the weights moved on)."""
         for name, ent in self.transposed.items():
-            if not ent[3] and ent[4] != self.version:
-                ops.transpose(self.c[name], ent[0])
-                ent[4] = self.version
+            if not ent.eager and ent.version != self.version:
+                ops.transpose(self.c[name], ent.t)
+                ent.version = self.version
 
     def name_at(self, off: int):
         """(parameter name, its first flat element) of the parameter that holds flat element `off`."""
-        import bisect
         if self._starts is None:
             self._starts = sorted((o, n) for n, o in self.offsets.items())
         i = bisect.bisect_right(self._starts, (off, chr(0x10ffff))) - 1
         return self._starts[i][1], self._starts[i][0]
 
     def pack_seg(self, name: str):
-        """(K, mode, [chunk0 x 4], stream pointer) of the stream-order packed copy the optimizer can maintain for the weight `name`
-        (adam_pack_table's eligibility rules), or None."""
-        _t, _n, _parts = self.adam_pack_table(0, self.total)
-        sg = self._adam_pack[(0, self.total, tuple(sorted(self.packed)))][3].get(name)
-        return None if sg is None else (sg[2], sg[3], list(sg[4]), sg[5])
+        """The AdamPackSeg of the stream-order packed copy the optimizer can maintain for the weight `name` (adam_pack_table's
+        eligibility rules), or None."""
+        return self._adam_pack_entry(0, self.total).segs.get(name)
 
     def adam_pack_table(self, a: int, b: int):
         """(device table of vct_adam_pack_seg, entries, [parts]) for the packed parts whose weights lie inside flat elements [a, b):
         the optimizer's pass over [a, b) writes their stream-order copies itself (ops.adam_step(pack=...)).  Parts with transposed
         blocks (the backward's stream) and matrices whose blocks are not whole 512-row blocks / 512-column slices stay with vct_ss_pack.
         The table is built once per (a, b) and set of streams (pointers are static)."""
+        hit = self._adam_pack_entry(a, b)
+        return hit.table, hit.nseg, hit.parts
+
+    def _adam_pack_entry(self, a: int, b: int) -> AdamPackEntry:
         key = (a, b, tuple(sorted(self.packed)))
         hit = self._adam_pack.get(key)
         if hit is not None:
-            return hit[:3]
-        import bisect
+            return hit
         starts = sorted((off, n) for n, off in self.offsets.items())
         segs, parts = {}, []
         c0 = self.cflat.data_ptr()
@@ -210,16 +283,15 @@ class ParamSet:
         # that two eligible streams hold, and the one nobody writes would go stale
         full = None
         if (a, b) != (0, self.total):
-            self.adam_pack_table(0, self.total)
-            full = set(id(x) for x in self._adam_pack[(0, self.total, key[2])][2])
+            full = set(id(x) for x in self._adam_pack_entry(0, self.total).parts)
         for ent in self.packed.values():
-            for sub in ent[2]:
-                if not (a <= sub[0] and sub[1] <= b):
+            for sub in ent.parts:
+                if not (a <= sub.start and sub.end <= b):
                     continue
                 if full is not None and id(sub) not in full:
                     continue
                 ok, mine = True, {}
-                for blk in sub[2]:
+                for blk in sub.blocks:
                     w, nch, dc = blk[:3]
                     if len(blk) > 3 and blk[3]:
                         ok = False
@@ -243,57 +315,59 @@ class ParamSet:
                     if dc >= 0xffff:
                         ok = False            # the kernels carry the first chunk of a block as a 16-bit field (0xffff = "not packed"): a
                         break                 # stream of >= 4 GiB stays with vct_ss_pack instead of silently going stale
-                    if name in segs and segs[name][5] != ent[0].data_ptr():
+                    if name in segs and segs[name].stream != ent.t.data_ptr():
                         ok = False            # another stream already holds this weight: the kernel's table has ONE stream per weight,
                         break                 # so this part stays with vct_ss_pack (refresh_transposed) instead of going stale
-                    sg = mine.setdefault(name, [mo, mo + N * K, K, mode, [-1, -1, -1, -1], ent[0].data_ptr()])
-                    if sg[3] != mode:
+                    sg = mine.get(name)
+                    if sg is None:
+                        sg = mine[name] = AdamPackSeg(mo, mo + N * K, K, mode, [-1, -1, -1, -1], ent.t.data_ptr())
+                    if sg.mode != mode:
                         ok = False
                         break
-                    sg[4][idx] = dc
+                    sg.chunk0[idx] = dc
                 if ok and mine:
                     segs.update(mine)
                     parts.append(sub)
-        rows = sorted(segs.values())
+        rows = sorted(segs.values(), key=lambda sg: sg.begin)      # (one segment per weight: the begins are distinct)
         if rows:
             arr = (ops.L.AdamPackSeg * len(rows))()
-            for i, (bg, en, K, mode, ch, ptr) in enumerate(rows):
-                arr[i].begin, arr[i].end, arr[i].K, arr[i].mode, arr[i].stream = bg, en, K, mode, ptr
+            for i, sg in enumerate(rows):
+                arr[i].begin, arr[i].end, arr[i].K, arr[i].mode, arr[i].stream = sg.begin, sg.end, sg.K, sg.mode, sg.stream
                 for j in range(4):
-                    arr[i].chunk0[j] = ch[j]
+                    arr[i].chunk0[j] = sg.chunk0[j]
             raw = bytes(arr)
             table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
         else:
             table = None
-        hit = self._adam_pack[key] = (table, len(rows), parts, segs)
-        return hit[:3]
+        hit = self._adam_pack[key] = AdamPackEntry(table, len(rows), parts, segs)
+        return hit
 
     def refresh_transposed(self, a: int, b: int, skip=(), packed_done=()):
         """Shadow elements [a, b) were just rewritten: eager transposed copies inside follow (except `skip`: already written by
         the optimizer's fused pass); lazy ones are picked up by want_transposed through `version`.  packed_done: parts of packed
         streams the optimizer's pass wrote itself (adam_pack_table)."""
         for name, ent in self.transposed.items():
-            if ent[3] and name not in skip and a <= ent[1] and ent[2] <= b:
-                ops.transpose(self.c[name], ent[0])
+            if ent.eager and name not in skip and a <= ent.start and ent.end <= b:
+                ops.transpose(self.c[name], ent.t)
         done = set(id(x) for x in packed_done)
         for ent in self.packed.values():
             todo = []
-            for sub in ent[2]:
+            for sub in ent.parts:
                 if id(sub) in done:
-                    sub[3] = False
+                    sub.dirty = False
                     continue
-                if sub[1] > a and sub[0] < b:                 # the rewritten range touches this part
-                    if a <= sub[0] and sub[1] <= b:
-                        todo += sub[2]
-                        sub[3] = False
+                if sub.end > a and sub.start < b:             # the rewritten range touches this part
+                    if a <= sub.start and sub.end <= b:
+                        todo += sub.blocks
+                        sub.dirty = False
                     else:                                     # partly rewritten (no schedule does this): re-pack at the next use
-                        sub[3] = True
+                        sub.dirty = True
             if todo:
-                ops.ss_pack(todo, ent[0])                     # every part of the stack this pass rewrote: one launch (<= 48 blocks)
+                ops.ss_pack(todo, ent.t)                      # every part of the stack this pass rewrote: one launch (<= 48 blocks)
 
     def eager_transposed_in(self, a: int, b: int):
         """[(name, tensor, start, end)] of the eager transposed copies whose weight lies inside flat elements [a, b)."""
-        return [(n, e[0], e[1], e[2]) for n, e in self.transposed.items() if e[3] and a <= e[1] and e[2] <= b]
+        return [(n, e.t, e.start, e.end) for n, e in self.transposed.items() if e.eager and a <= e.start and e.end <= b]
 
     def install_grads(self):
         for n, p in self.params.items():

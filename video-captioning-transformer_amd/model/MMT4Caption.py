@@ -80,6 +80,7 @@ class MMT4Caption(nn.Module):
         self._ps: Optional[ParamSet] = None
         self._unit_loss_grad = False
         self._seed = None
+        self._pending_enc_bwd = None      # train_step_kernels(defer_join=True): the encoder backward, not enqueued yet
         self._build_flat()
 
     # ---- flat parameter storage --------------------------------------------------------------------
@@ -192,7 +193,7 @@ class MMT4Caption(nn.Module):
     def launch_encoder_backward(self, main: bool = False):
         """main: enqueue it on the CURRENT stream (the caller has joined the side stream: d(memory) is final) -- for the one-launch
         sample-stationary backward, which takes whole compute units and gains nothing from running beside other kernels."""
-        fn, self._pending_enc_bwd = getattr(self, "_pending_enc_bwd", None), None
+        fn, self._pending_enc_bwd = self._pending_enc_bwd, None
         if fn is not None:
             fn(main)
 

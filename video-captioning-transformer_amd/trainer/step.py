@@ -1,0 +1,272 @@
+"""The step executor of the caption task (CaptionTrainer: eager, recorded launch list or captured hipGraph) and the epoch loop."""
+from typing import Optional
+import os
+
+import torch
+import torch.distributed as dist
+
+from .. import ops
+from ..engine import first_input, stage_inputs, static_inputs
+from ..utils import capture_graph
+from .exchange import GradExchange, ShardedExchange
+from .optim import FusedAdam
+
+
+class CaptionTrainer:
+    """One object = the reference's `model(...) -> zero_grad -> backward -> step` loop body
+    (train.py:123-126) on the kernel fast path, with the gradient exchange folded into backward.
+
+    Executors of the ~100-launch step (single GPU, FusedAdam):
+      * eager (default off the GPU fast path): Python issues every launch through ctypes;
+      * launch_list=True: the step is recorded ONCE per input shape into a C-side launch list (ops.LaunchList:
+        every launch with its stream, every cross-stream edge) and re-issued by one C call per step -- eager
+        two-stream semantics without the Python/ctypes cost per launch;
+      * use_graph=True: the step is captured into a hipGraph (bitwise equal, but replay serialises the two streams).
+    Inputs are copied into static buffers; the dropout seed, the Adam step counter and the Adam hyper-parameters live
+    in device memory, so every replay sees fresh values.  Recordings are dropped when an activation buffer of THIS model had
+    to grow (engine/params.py: StepContext.generation), because they bake device pointers."""
+
+    def __init__(self, model, optimizer, exchange: Optional[GradExchange] = None, use_graph: bool = False,
+                 launch_list: Optional[bool] = None, keep_weight_grads: Optional[bool] = None):
+        """keep_weight_grads: on the single-GPU bf16 FusedAdam path the 2-D weights are stepped inside their weight-gradient GEMMs and
+        their gradients are NOT stored (model.grads_valid is False after a step; the reference leaves valid .grad after backward,
+        train.py:125).  True stores them as well (for clipping, logging, hooks; costs the 4 B per parameter the fusion saved);
+        None: the VCT_FUSE_ADAM_KEEP_GRAD environment switch (default off)."""
+        self.model, self.opt, self.ex = model, optimizer, exchange
+        fused = self._fused = isinstance(optimizer, FusedAdam)
+        if keep_weight_grads is not None and fused:
+            optimizer.set_keep_grads(bool(keep_weight_grads))
+        model._unit_loss_grad = True
+        single = (exchange is None or not exchange.active) and fused
+        # a launch list can also carry the exchange when every collective is recordable: stream work of the library's own RCCL
+        # communicator, or host commands of the list (comm.C10dColl under ops.host_call: the one-GPU multi-rank tests)
+        listable = single or (isinstance(exchange, ShardedExchange) and getattr(exchange.coll, "recordable", False))
+        self.use_graph = bool(use_graph) and single
+        self.use_list = (bool(launch_list) if launch_list is not None else False) and listable and not self.use_graph
+        # recordings per input shape, as (recording, its loss tensor): launch lists / captured graphs, both replayed by .replay()
+        self._lists = {}
+        self._graphs = {}
+        self._static = {}                 # per input shape: the static input buffers the recordings read
+        self._gen = None                  # the buffer generation (engine.StepContext) the recordings were made at
+        if single and model.flat_grads.is_cuda:
+            # this trainer (zero_grad implicit, no exchange, no in-place averaging) is the only writer of the gradient buffer
+            model.cap_decoder._engine().exclusive_grads = True
+        # single GPU: per-bucket Adam on the side stream was measured SLOWER (3.28 vs 3.14 ms/step: the 6.5 TB/s
+        # optimizer pass steals HBM bandwidth from the GEMMs it overlaps), so it is opt-in; with a gradient exchange
+        # Adam always runs per bucket as each all-reduce lands (it overlaps the wire, not the GEMMs)
+        self.overlap_adam = False
+        # single GPU, FusedAdam, bf16: every weight matrix is stepped in the epilogue of its own weight-gradient GEMM (FusedAdam.
+        # enable_dw_fusion); the hook is installed only WHILE this trainer enqueues a step (a plain loss.backward() outside it must
+        # keep producing gradients and nothing else)
+        self.fuse_adam = bool(single and optimizer.fuse_dw_default
+                              and model._ps.compute_dtype == torch.bfloat16 and model.flat_grads.is_cuda)
+
+    # A/B switch (single GPU): the whole Adam pass after the joined backward instead of 86 % of it beside the encoder backward
+    adam_after_backward = os.environ.get("VCT_ADAM_TAIL", "0") == "1"
+    warm_streams = os.environ.get("VCT_WARM_STREAMS", "1") != "0"
+
+    def _step_kernels(self, feats, mask, ids):
+        if not self.fuse_adam:
+            return self._step_kernels_body(feats, mask, ids)
+        self.opt.enable_dw_fusion(True)
+        self.opt.begin_step()
+        try:
+            return self._step_kernels_body(feats, mask, ids)
+        finally:
+            self.opt.enable_dw_fusion(False)
+
+    def _step_kernels_body(self, feats, mask, ids):
+        m = self.model
+        fused = self._fused
+        ops.tap("step", 0)
+        if not fused:
+            m._ps.masters_written()               # a torch optimizer wrote the fp32 masters: re-cast the shadow
+        else:
+            m._ps.refresh_shadow()                # FusedAdam keeps the shadow current (first step: cast once)
+        exchanging = self.ex is not None and self.ex.active
+        if exchanging and isinstance(self.ex, ShardedExchange):
+            # reduce-scatter -> Adam on the owned shard -> all-gather, per bucket, on the communicator's stream
+            loss = m.train_step_kernels(feats, mask, ids, bucket_ready=self.ex.bucket_ready)
+            self.ex.finish()
+        elif exchanging:
+            loss = m.train_step_kernels(feats, mask, ids, bucket_ready=self.ex.bucket_ready)
+            if fused:                             # Adam per bucket as its averaged gradient lands
+                self.ex.finish(on_bucket_done=self.opt.step_range)
+                self.opt.finish_ranges()
+            else:
+                self.ex.finish()
+                self.opt.step()
+        elif fused and self.overlap_adam and first_input(feats).is_cuda:
+            # single GPU: Adam on each gradient bucket the moment backward completes it, on the side stream, so the
+            # 1.4 GB optimizer pass hides under the rest of backward instead of trailing it
+            buckets = m.grad_buckets()
+            ctx = m._ps.ctx
+
+            def hook(i):
+                side = ctx.side
+                if side is None:
+                    self.opt.step_range(*buckets[i])
+                    return
+                ops.stream_wait(side, None)
+                with torch.cuda.stream(side):
+                    self.opt.step_range(*buckets[i])
+            loss = m.train_step_kernels(feats, mask, ids, bucket_ready=hook)   # zero_grad is implicit: grads are overwritten
+            if ctx.side is not None:
+                ops.stream_wait(None, ctx.side)
+            self.opt.finish_ranges()
+        elif fused and first_input(feats).is_cuda and m.overlap_enc_bwd and not self.adam_after_backward:
+            # the encoder backward is still running on the side stream when the decoder's tail is done: Adam on everything
+            # but the encoder (86 % of the parameters at cfg-B) fills that gap on the main stream, the rest follows the join
+            loss = m.train_step_kernels(feats, mask, ids, defer_join=True)
+            a = m.encoder_param_begin
+            # the decoder layers' weight gradients and the d(memory) GEMMs were issued on the SIDE stream: Adam reads
+            # those gradients and rewrites the weights those kernels read, so the main stream joins the side stream first
+            # (it is idle here: the encoder backward has not been enqueued yet)
+            m.cap_decoder._engine().join_side()
+            if m.encoder_backward_is_one_launch():
+                # the sample-stationary backward takes whole compute units: alone on the main stream, ahead of the optimizer's pass; its
+                # weight-gradient GEMMs (side stream) then run beside that pass
+                m.launch_encoder_backward(main=True)
+            ops.tap("adam", 0)
+            self.opt.step_range(0, a)            # enqueued BEFORE the encoder backward: one launch vs ~35
+            ops.tap("adam", 1)
+            m.launch_encoder_backward()
+            m.join_backward()
+            self.opt.step_range(a, m._ps.total)
+            self.opt.finish_ranges()
+        else:
+            loss = m.train_step_kernels(feats, mask, ids)
+            self.opt.step()
+        if self.warm_streams and first_input(feats).is_cuda:
+            # the next step begins with the two sample-stationary stack launches, which stream these packed weights chunk by chunk with
+            # two chunks of prefetch: behind the optimizer's passes (1.4 GB of traffic through the memory-side cache) every chunk is an
+            # HBM miss
+            for stream in m._ps.packed.values():
+                ops.warm(stream.t)
+        if m.training and m.video_encoder.cfg["dropout"] > 0:
+            ops.advance_seed(m._seed)
+        ops.tap("step", 1)
+        return loss
+
+    def _fresh_shadow(self):
+        """Replays skip _step_kernels, which is where the bf16 shadow / transposed copies follow the fp32 masters: if the
+        masters were written outside FusedAdam since the last step (load_state_dict, load_weights, restoring the best
+        checkpoint), re-cast them eagerly on the current stream before the replay (host-only version-stamp check otherwise)."""
+        self.model._ps.refresh_shadow()
+
+    def drop_recordings(self):
+        """Forget every recorded launch list / captured graph (they are re-made on the next step of each shape): needed after
+        anything that changes WHAT a step launches, e.g. ops.taps_enable(...)."""
+        self._lists.clear()
+        self._graphs.clear()
+
+    def _static_inputs(self, key, feats, mask, ids):
+        s = self._static.get(key)
+        if s is None:
+            s = self._static[key] = (static_inputs(feats), static_inputs(mask), ids.clone())
+        else:
+            # a caller that already works in the static buffers (adopt_inputs) skips the staging copies: three small device copies
+            # and the launch gaps around them are ~35 us at the head of a 2.4 ms step
+            stage_inputs(s[0], feats, non_blocking=True)
+            if mask is not None:
+                stage_inputs(s[1], mask, non_blocking=True)
+            if s[2].data_ptr() != ids.data_ptr():
+                s[2].copy_(ids, non_blocking=True)
+        return s
+
+    def _input_key(self, feats, mask, ids):
+        if isinstance(feats, (list, tuple)):       # one tensor per modality
+            return (tuple((tuple(f.shape), f.dtype) for f in feats), None if mask is None else tuple(tuple(m.shape) for m in mask),
+                    tuple(ids.shape), self.model.training)
+        return (tuple(feats.shape), feats.dtype, None if mask is None else tuple(mask.shape), tuple(ids.shape), self.model.training)
+
+    def adopt_inputs(self, feats, mask, ids: torch.Tensor):
+        """The trainer's own static input buffers for this shape, initialised with the given batch.  Recorded launch lists and
+        captured graphs read their inputs from these buffers, so step() normally copies every batch into them; a producer that
+        writes its batches INTO them (a device-side loader, a benchmark with resident data) and passes them to step() has no copy
+        left.  Returns (feats, mask, ids) views of the buffers; without a recording executor the inputs are returned unchanged.
+        feats / mask: a tensor, or one tensor per modality (mask: that list or None)."""
+        if not (self.use_graph or self.use_list):
+            return feats, mask, ids
+        return self._static_inputs(self._input_key(feats, mask, ids), feats, mask, ids)
+
+    def _check_generation(self):
+        """Recordings bake device pointers: drop them when a buffer of this model grew (or a packed stream appeared) since they were made."""
+        gen = self.model._ps.ctx.generation
+        if self._gen != gen:
+            self.drop_recordings()
+            self._gen = gen
+
+    def _record_list(self, static):
+        ll = ops.LaunchList()
+        with ll.record():                           # recording executes nothing
+            loss = self._step_kernels(*static)
+        return ll, loss
+
+    def _capture_graph(self, static):
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        try:
+            with capture_graph(graph):
+                loss = self._step_kernels(*static)
+        except Exception:                           # capture is an optimisation, never a requirement
+            self.use_graph = False
+            return None
+        return graph, loss
+
+    def step(self, feats, mask, ids: torch.Tensor) -> torch.Tensor:
+        """Returns this rank's loss as a device tensor [1] (no host sync).  feats / mask: a tensor (one modality), or one tensor
+        per modality (mask: that list or None)."""
+        if self._fused:
+            self.opt.sync_hyper()
+        if not (self.use_graph or self.use_list):
+            return self._step_kernels(feats, mask, ids)
+        self._check_generation()
+        key = self._input_key(feats, mask, ids)
+        static = self._static_inputs(key, feats, mask, ids)
+        cache, record = (self._lists, self._record_list) if self.use_list else (self._graphs, self._capture_graph)
+        hit = cache.get(key)
+        if hit is None:
+            # first step of this shape: run it eagerly on the static copies (allocates every buffer), then record the same
+            # schedule; later calls replay the recording
+            eager_loss = self._step_kernels(*static).clone()
+            self._check_generation()                # the eager step allocated: older recordings are stale, this one is not made yet
+            hit = record(static)
+            if hit is not None:
+                cache[key] = hit
+            return eager_loss
+        recording, loss = hit
+        self._fresh_shadow()
+        recording.replay()
+        self.model._ps.shadow_replayed()            # the replayed optimizer rewrote the shadow
+        return loss
+
+
+def train_epoch(model, optimizer, dataloader, mode: str = "caption", exchange: Optional[GradExchange] = None,
+                log_every: int = 0):
+    """reference train.py:113-148 for mode != 'cross'.  `dataloader` yields (v_feats, v_masks, captions, vids)
+    with the reference's layouts (lists of tensors; captions = id rows or strings).  Returns the epoch-mean of
+    the all-rank mean loss -- one device->host sync per epoch instead of one per step."""
+    if mode != "caption":
+        raise NotImplementedError("only the caption task is on the accelerated path")
+    model.train()
+    model.mode(mode)
+    trainer = CaptionTrainer(model, optimizer, exchange)
+    dev = model.flat_params.device
+    total = torch.zeros(1, device=dev)
+    n = 0
+    n_modal = model.video_encoder.num_modal
+    for v_feats, v_masks, captions, _vids in dataloader:
+        if n_modal > 1:      # every modality (MMEncoder.forward takes the lists)
+            feats = [f.to(dev, non_blocking=True) for f in v_feats]
+            mask = [m.to(dev, non_blocking=True) for m in v_masks] if v_masks is not None else None
+        else:
+            feats = v_feats[0].to(dev, non_blocking=True)
+            mask = v_masks[0].to(dev, non_blocking=True) if v_masks is not None else None
+        ids, _ = model.cap_preprocessor(captions)
+        total += trainer.step(feats, mask, ids)
+        n += 1
+    if exchange is not None and exchange.world > 1:
+        dist.all_reduce(total, op=dist.ReduceOp.SUM, group=exchange.group)
+        total /= exchange.world
+    return float(total) / max(n, 1)
