@@ -328,6 +328,61 @@ int vct_mm_frontend_fwd(const vct_mm_frontend_desc* d, void* stream);
 int vct_mm_frontend_bwd(const vct_mm_frontend_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Encoder front end with every option of the reference's `mme` block, n = 1 .. VCT_MM_MAX_MODAL feature streams
+ * (csrc/vct_enc_frontend_ex.hip).  Row layout, vector width rules and the fixed-order reductions are those of vct_mm_frontend_*
+ * (which, like vct_enc_frontend_*, stays the path of the shipped `avg` / `encoding` / no-norm combination).
+ *   fwd, one launch:
+ *        pre[b, off_i]     = (temporal(off_i)     + modal_w[labels[off_i]])     + agg_t u_i[b, t]
+ *        pre[b, off_i+1+t] = (temporal(off_i+1+t) + modal_w[labels[off_i+1+t]]) + u_i[b, t]
+ *        agg      = VCT_AGG_MEAN: fp32 mean, or VCT_AGG_MAX: maximum, over ALL T_i rows in row order, pads included
+ *                   (GlobalAggregation 'avg' / 'max' = AdaptiveAvgPool1d(1) / AdaptiveMaxPool1d(1), MMEncoder.py:173-197)
+ *        temporal = VCT_TEMPORAL_FIXED: temp[s] (fp32 [S, d], the TemporalEncoding rows, MMEncoder.py:83-104), or
+ *                   VCT_TEMPORAL_LEARNED: emb_w[tidx[s]] (emb_w fp32 [emb_rows, d] = temp_emb.embedding.weight, tidx int32 [S] built by
+ *                   the host: 0 on aggregation rows, linspace(1, T_0, T_i) as int32 on frame rows, MMEncoder.py:118-160; an index
+ *                   outside [0, emb_rows) reads no row and gets no gradient)
+ *        modal    = as vct_mm_frontend_fwd; n == 1 has none (modal_w, labels, d_modal unused and may be NULL, MMEncoder.py:232,271)
+ *        x0 = pre, or with norm != 0:  x0 = dropout(LayerNorm(pre))  (gamma / beta fp32 [d], eps 1e-5; the dropout comes AFTER the
+ *        norm, MMEncoder.py:240-242,272-273); mean / rstd fp32 [B*S] are stored for the backward; mask(site, b*S*d + s*d + c) of
+ *        vct_common.h's counter hash, p_drop == 0 or seed == NULL: no dropout.  key_pad as vct_mm_frontend_fwd.
+ *   bwd: dpre = dx, or with norm != 0 the LayerNorm backward of (dx x the same mask) per row, with pre recomputed from u in fp32;
+ *        its column partials go to param_ws (fp32 [B*n][2][d]: one row pair per (sample, stream), to be finalized by
+ *        vct_ln_param_finalize_batched with B*n rows) and dpre itself, in fp32, to the caller's buffer `dpre` [B*S, d].
+ *        du_i[b, t] = dpre[b, off_i+1+t] + share of dpre[b, off_i]: / T_i (mean), or the whole value on the FIRST row that holds
+ *        the column's maximum of u_i[b, :, c] (max; recomputed from u, which the caller keeps; ties go to the lower row like
+ *        torch's max-pool backward).  d_modal as vct_mm_frontend_bwd.  d_emb fp32 [emb_rows, d] is WRITTEN in full: row e = sum over
+ *        b and the rows s with tidx[s] == e of dpre[b, s, :], zeros where nobody reads e.  No atomics; bitwise reproducible.
+ *        One launch; with norm != 0 and a modal or learned-temporal gradient to form, those sums over all samples run as a second
+ *        launch behind the first (they read every sample's dpre; no in-launch hand-off between workgroups).
+ * d a multiple of 8 (bf16) / 4 (fp32) and <= 1024 (a row lives in one wave's registers), S <= 1024, pointers 16-byte aligned.
+ * --------------------------------------------------------------------------------------------- */
+#define VCT_AGG_MEAN 0
+#define VCT_AGG_MAX 1
+#define VCT_TEMPORAL_FIXED 0
+#define VCT_TEMPORAL_LEARNED 1
+typedef struct vct_enc_frontend_ex_desc {
+  int32_t dtype, n, B, d;
+  int32_t n_labels, agg, temporal, norm;
+  int32_t emb_rows; uint32_t site; float p_drop; int32_t reserved;
+  int32_t T[VCT_MM_MAX_MODAL];
+  const void* u[VCT_MM_MAX_MODAL];          /* fwd, and bwd when agg == MAX or norm: [B*T_i, d] */
+  const uint8_t* mask[VCT_MM_MAX_MODAL];    /* fwd: [B, T_i] (1 = padded) or NULL */
+  const float* temp;                        /* FIXED: [S, d] */
+  const float* emb_w; const int32_t* tidx;  /* LEARNED: [emb_rows, d], [S] */
+  const float* modal_w; const int32_t* labels;
+  const float* gamma; const float* beta;    /* norm: [d] (beta: fwd only) */
+  const uint32_t* seed;
+  void* x0; uint8_t* key_pad;               /* fwd outputs: [B*S, d], [B, S] */
+  float* mean; float* rstd;                 /* norm: [B*S], written by fwd, read by bwd */
+  const void* dx;                           /* bwd: [B*S, d] */
+  void* du[VCT_MM_MAX_MODAL];               /* bwd: [B*T_i, d] */
+  float* d_modal;                           /* bwd, n >= 2: [n_labels, d] */
+  float* d_emb;                             /* bwd, LEARNED: [emb_rows, d] */
+  float* dpre; float* param_ws;             /* bwd, norm: fp32 [B*S, d], fp32 [B*n][2][d] */
+} vct_enc_frontend_ex_desc;
+int vct_enc_frontend_ex_fwd(const vct_enc_frontend_ex_desc* d, void* stream);
+int vct_enc_frontend_ex_bwd(const vct_enc_frontend_ex_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Token embedding: x[n] = dropout(table[ids[n]] + pos[n % S])   (no sqrt(d) scaling)
  * replaces: nn.Embedding(padding_idx) + PositionalEmbedding (CapDecoder.py:26,48; Embedding.py:23-25).
  * ids: int64 [N] read with element stride id_stride from ids + b*id_batch_stride (so the token-shift

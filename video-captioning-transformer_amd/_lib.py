@@ -121,6 +121,20 @@ class MmFrontendDesc(C.Structure):
                 ("du", vp * MM_MAX_MODAL), ("d_modal", vp)]
 
 
+AGG = {"avg": 0, "max": 1}
+TEMPORAL = {"encoding": 0, "embedding": 1}
+
+
+class EncFrontendExDesc(C.Structure):
+    """include/vct_hip.h, vct_enc_frontend_ex_desc: the encoder front end with every `mme` option."""
+    _fields_ = [("dtype", i32), ("n", i32), ("B", i32), ("d", i32), ("n_labels", i32), ("agg", i32), ("temporal", i32), ("norm", i32),
+                ("emb_rows", i32), ("site", u32), ("p_drop", f32), ("reserved", i32),
+                ("T", i32 * MM_MAX_MODAL), ("u", vp * MM_MAX_MODAL), ("mask", vp * MM_MAX_MODAL),
+                ("temp", vp), ("emb_w", vp), ("tidx", vp), ("modal_w", vp), ("labels", vp), ("gamma", vp), ("beta", vp), ("seed", vp),
+                ("x0", vp), ("key_pad", vp), ("mean", vp), ("rstd", vp), ("dx", vp), ("du", vp * MM_MAX_MODAL),
+                ("d_modal", vp), ("d_emb", vp), ("dpre", vp), ("param_ws", vp)]
+
+
 DEC_PRO = {"none": 0, "embed": 1, "ln": 2, "ln_ln": 3, "self_attn": 4, "cross_attn": 5}
 
 _SIGS = {
@@ -148,6 +162,8 @@ _SIGS = {
     "vct_enc_frontend_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "vct_mm_frontend_fwd": (C.c_int, [C.POINTER(MmFrontendDesc), vp]),
     "vct_mm_frontend_bwd": (C.c_int, [C.POINTER(MmFrontendDesc), vp]),
+    "vct_enc_frontend_ex_fwd": (C.c_int, [C.POINTER(EncFrontendExDesc), vp]),
+    "vct_enc_frontend_ex_bwd": (C.c_int, [C.POINTER(EncFrontendExDesc), vp]),
     "vct_embed_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, vp, vp, vp, u32, f32, vp]),
     "vct_embed_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, i64, vp, vp, vp, i64, C.c_int, vp, u32, f32, vp]),
     "vct_sce_loss": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, i64, f32, vp, vp, i64, vp, vp]),

@@ -4,21 +4,27 @@ import os
 import torch
 
 from .. import ops
-from .stack import ENC_SITE, _StackBase
+from .stack import ENC_IN_SITE, ENC_SITE, _StackBase
 
 
 class EncoderEngine(_StackBase):
-    """MultiModalEncoder ('avg' aggregation token, sinusoidal temporal encoding; one modality, or n >= 2 with the modal
-    embedding): model/MMEncoder.py:12-48, 83-104, 244-276."""
+    """MultiModalEncoder: model/MMEncoder.py:12-48, 83-104, 244-276.  The shipped combination ('avg' aggregation token, sinusoidal
+    temporal encoding, no input norm; one modality, or n >= 2 with the modal embedding) runs on its own front-end kernels; any other
+    combination of cfg's global_type ('avg' | 'max'), temporal_type ('encoding' | 'embedding') and do_norm (MMEncoder.py:118-197,
+    240-242) goes through vct_enc_frontend_ex_* (_forward_streams(ex=True))."""
 
     # A/B switch: 1 = a side-stream backward puts the upper layers' weight-gradient groups behind the main stream's tail, 2 = all, 0 = none
     enc_dw_main = int(os.environ.get("VCT_ENC_DW_MAIN", "1"))
 
     def __init__(self, ps, prefix, cfg, seed, pe_buffer: torch.Tensor):
         super().__init__(ps, prefix, cfg, seed)
-        self.pe = pe_buffer  # [1, 512, d] fp32 buffer `temp_emb.pe`
+        self.pe = pe_buffer  # [1, 512, d] fp32 buffer `temp_emb.pe` (None with the learned temporal embedding)
         self._pe_rows = {}
         self._mm_rows = {}
+        self._ex_rows = {}
+        self.learned, self.by_max, self.do_norm = (cfg.get("temporal_type", "encoding") == "embedding", cfg.get("global_type", "avg") == "max",
+                                                   bool(cfg.get("do_norm", False)))
+        self.variant = self.learned or self.by_max or self.do_norm      # anything but the shipped combination
         self.mm_Ts = None    # frame counts of the modalities of the current shape (None: one modality)
         ls = range(cfg["layers"])      # per layer: parameter prefix, buffer tag, dropout site base (lists for _stack_ss; the unfused loops index them)
         self.lps, self.tags, self.sites = [f"transformer_encoder.layers.{l}." for l in ls], [f"L{l}." for l in ls], [ENC_SITE + 16 * l for l in ls]
@@ -43,6 +49,43 @@ class EncoderEngine(_StackBase):
             self._pe_rows[T] = r
         return r
 
+    @staticmethod
+    def temporal_index(Ts):
+        """Rows of temp_emb.embedding.weight the memory rows read (TemporalEmbedding, MMEncoder.py:150-158): 0 on every aggregation
+        row, np.linspace(1, T_0, T_i) as int32 on the frames of stream i."""
+        import numpy as np
+        return np.concatenate([np.concatenate([np.zeros(1, np.int32), np.linspace(1, Ts[0], t).astype(np.int32)]) for t in Ts])
+
+    def ex_rows(self, Ts):
+        """The per-shape tables of vct_enc_frontend_ex_*, built once per frame-count tuple: dict(temp | tidx, labels)."""
+        r = self._ex_rows.get(Ts)
+        if r is None:
+            n = len(Ts)
+            r = {"labels": None}
+            if self.learned:
+                idx = self.temporal_index(Ts)
+                rows = self.F("temp_emb.embedding.weight").shape[0]
+                if int(idx.max()) >= rows:
+                    raise ValueError(f"temporal embedding: {Ts[0]} frames in the first stream need row {int(idx.max())} of a table of {rows}")
+                r["tidx"] = torch.from_numpy(idx).to(self.dev)
+            if not self.learned:      # the fixed table (and, with several streams, the labels) are the shipped paths' own
+                r["temp"], r["labels"] = self.mm_rows(Ts) if n > 1 else (self.pe_rows(Ts[0]), None)
+            elif n > 1:
+                r["labels"] = self._mm_labels(Ts)
+            self._ex_rows[Ts] = r
+        return r
+
+    def _mm_labels(self, Ts):
+        n, diff = len(Ts), self.cfg.get("modal_different", True)
+        labels = []
+        for i, t in enumerate(Ts):
+            labels += [i + n if diff else i] + [i] * t
+        rows = self.F("modal_emb.modal_emb.weight").shape[0]
+        if sorted(set(labels)) != list(range(rows)):
+            raise ValueError(f"modal-embedding labels {sorted(set(labels))} do not cover the {rows} rows of modal_emb exactly "
+                             f"(n = {n}, modal_different = {diff})")
+        return torch.tensor(labels, dtype=torch.int32).to(self.dev)
+
     def mm_rows(self, Ts):
         """(temporal rows fp32 [S, d], row labels int32 [S]) of the multi-modal front end for the frame counts Ts, cached per Ts.
         Row t of modality i gets pe[idx_i[t]], idx_i = linspace(0, T_0 - 1, T_i) as int32 (MMEncoder.py:89-104), its aggregation
@@ -50,21 +93,16 @@ class EncoderEngine(_StackBase):
         r = self._mm_rows.get(Ts)
         if r is None:
             import numpy as np
-            n, d, diff = len(Ts), self.cfg["d"], self.cfg.get("modal_different", True)
+            d = self.cfg["d"]
             temp = torch.zeros(sum(t + 1 for t in Ts), d, dtype=torch.float32, device=self.dev)
-            labels, at = [], 0
+            at = 0
             for i, t in enumerate(Ts):
                 idx = torch.from_numpy(np.linspace(0, Ts[0] - 1, t).astype(np.int32).astype(np.int64)).to(self.dev)
                 temp[at + 1:at + 1 + t] = self.pe[0, idx, :]
-                labels += [i + n if diff else i] + [i] * t
                 at += t + 1
-            # the kernels take the table as given (a row with an out-of-range label gets no modal row and no gradient): check it here,
-            # once per shape, against the embedding it indexes -- every row of the table must be used, and nothing else
-            rows = self.F("modal_emb.modal_emb.weight").shape[0]
-            if sorted(set(labels)) != list(range(rows)):
-                raise ValueError(f"modal-embedding labels {sorted(set(labels))} do not cover the {rows} rows of modal_emb exactly "
-                                 f"(n = {n}, modal_different = {diff})")
-            r = self._mm_rows[Ts] = (temp, torch.tensor(labels, dtype=torch.int32).to(self.dev))
+            # the kernels take the table as given (a row with an out-of-range label gets no modal row and no gradient): _mm_labels checks
+            # it here, once per shape, against the embedding it indexes -- every row of the table must be used, and nothing else
+            r = self._mm_rows[Ts] = (temp, self._mm_labels(Ts))
         return r
 
     def forward(self, feats, mask, training: bool) -> torch.Tensor:
@@ -74,9 +112,13 @@ class EncoderEngine(_StackBase):
         got = len(feats) if isinstance(feats, (list, tuple)) else 1
         if got != n:        # (a stream short would leave its unify / modal-embedding gradients unwritten: stale ones get stepped)
             raise ValueError(f"the encoder has {n} feature stream(s), got {got}" + (" (a bare tensor)" if n > 1 and got == 1 else ""))
+        if self.variant:
+            many = isinstance(feats, (list, tuple))
+            return self._forward_streams(list(feats) if many else [feats], (list(mask) if many else [mask]) if mask is not None else None,
+                                         training, ex=True)
         if isinstance(feats, (list, tuple)):
             if n > 1:
-                return self._forward_mm(feats, mask, training)
+                return self._forward_streams(feats, mask, training)
             feats, mask = feats[0], (mask[0] if mask is not None else None)
         self.mm_Ts = None
         B, T, Ein = feats.shape
@@ -109,9 +151,11 @@ class EncoderEngine(_StackBase):
         x = ops.enc_frontend_fwd(u, self.pe_rows(T), b.get("x0", (M, d), self.dt), B, T)
         return self._stack_fwd(b, x, B, Te, kpm)      # (features of another width: the front end stays on its own kernels)
 
-    def _forward_mm(self, feats, masks, training: bool) -> torch.Tensor:
-        """n >= 2 modalities: per-modality input cast and unify GEMM, ONE front-end launch (vct_mm_frontend_fwd: aggregation rows,
-        temporal rows, modal embedding, the [B, S] key padding), then the stack (MMEncoder.py:244-274)."""
+    def _forward_streams(self, feats, masks, training: bool, ex: bool = False) -> torch.Tensor:
+        """A list of feature streams: per-stream input cast and unify GEMM, ONE front-end launch, then the stack (MMEncoder.py:244-274).
+        ex = False (the shipped combination, n >= 2): vct_mm_frontend_fwd -- aggregation rows, temporal rows, modal embedding, the
+        [B, S] key padding.  ex = True (any other combination, n >= 1): vct_enc_frontend_ex_fwd -- aggregation by mean or max, fixed or
+        learned temporal rows, modal embedding, Dropout(LayerNorm(.)), key padding."""
         B = feats[0].shape[0]
         Ts = tuple(int(f.shape[1]) for f in feats)
         d = self.cfg["d"]
@@ -138,12 +182,29 @@ class EncoderEngine(_StackBase):
         if masks is not None:
             mks = [self._mask_u8(m) for m in masks]
             kp = b.get("mm_kpm", (B, S), torch.uint8)
-        temp, labels = self.mm_rows(Ts)
-        x = ops.mm_frontend_fwd(us, mks, temp, self.F("modal_emb.modal_emb.weight"), labels, b.get("x0", (B * S, d), self.dt), kp,
-                                B, Ts)
+        if ex:
+            x = ops.enc_frontend_ex_fwd(us, mks, b.get("x0", (B * S, d), self.dt), kp, B, Ts, **self._ex_args(b, B, Ts))
+        else:
+            temp, labels = self.mm_rows(Ts)
+            x = ops.mm_frontend_fwd(us, mks, temp, self.F("modal_emb.modal_emb.weight"), labels, b.get("x0", (B * S, d), self.dt), kp,
+                                    B, Ts)
         kpm = (kp, 0) if kp is not None else None     # the [B, S] mask, no shift: both attention paths read it as is
         b.t["kpm_used"] = kpm
         return self._stack_fwd(b, x, B, S, kpm)
+
+    def _ex_args(self, b, B, Ts):
+        """What both directions of vct_enc_frontend_ex_* take besides the activations (ops.enc_frontend_ex_fwd / _bwd)."""
+        rows, S = self.ex_rows(Ts), sum(t + 1 for t in Ts)
+        kw = dict(agg="max" if self.by_max else "avg", labels=rows["labels"],
+                  modal_w=self.F("modal_emb.modal_emb.weight") if len(Ts) > 1 else None)
+        if self.learned:
+            kw.update(tidx=rows["tidx"], emb_w=self.F("temp_emb.embedding.weight"))
+        else:
+            kw.update(temp=rows["temp"])
+        if self.do_norm:
+            kw["norm"] = dict(gamma=self.F("norm.weight"), beta=self.F("norm.bias"), mean=b.get("in.mean", (B * S,), torch.float32),
+                              rstd=b.get("in.rstd", (B * S,), torch.float32), dropout=self.drop(ENC_IN_SITE))
+        return kw
 
     def _stack_fwd(self, b, x, B, Te, kpm) -> torch.Tensor:
         """The encoder stack on its input x [B*Te, d]: sample-stationary when _ss_ok allows it, else layer by layer."""
@@ -177,7 +238,20 @@ class EncoderEngine(_StackBase):
             return
         Ts = self.mm_Ts
         dus = [b.get(f"du{i}", (B * t, d), self.dt) for i, t in enumerate(Ts)]
-        ops.mm_frontend_bwd(dx, dus, self.G("modal_emb.modal_emb.weight"), self.mm_rows(Ts)[1], B, Ts)
+        if self.variant:
+            # ONE launch (two with the norm: the parameter sums behind the rows); the gradients of temp_emb.embedding.weight and
+            # modal_emb are WRITTEN, the norm's partials join the batched LayerNorm-parameter finalize (flush_ln_grads)
+            n, S = len(Ts), T + 1
+            kw = self._ex_args(b, B, Ts)
+            if self.do_norm:
+                ws = b.get("in.ln_ws", (B * n * 2 * d,), torch.float32)
+                kw.update(dpre=b.get("in.dpre", (B * S, d), torch.float32), param_ws=ws)
+                self._ln_pending.append((ws.data_ptr(), self.G("norm.weight").data_ptr(), self.G("norm.bias").data_ptr(), B * n))
+            ops.enc_frontend_ex_bwd(dx, dus, B, Ts, us=[b.t[f"u{i}"] for i in range(n)],
+                                    d_modal=self.G("modal_emb.modal_emb.weight") if n > 1 else None,
+                                    d_emb=self.G("temp_emb.embedding.weight") if self.learned else None, **kw)
+        else:
+            ops.mm_frontend_bwd(dx, dus, self.G("modal_emb.modal_emb.weight"), self.mm_rows(Ts)[1], B, Ts)
         for i, du in enumerate(dus):
             self.dw_gemm(du, b.t[f"x_in{i}"], self.G(f"unify.{i}.weight"), bias_grad=self.G(f"unify.{i}.bias"))
 

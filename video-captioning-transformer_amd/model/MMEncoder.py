@@ -1,13 +1,13 @@
-"""MultiModalEncoder -- drop-in for the reference's model/MMEncoder.py:205-276 (`temporal: "encoding"`, `aggregation: "avg"`,
-do_norm False; one or more modalities), executed by hand-written gfx950 kernels (engine/encoder.py: EncoderEngine).  Same constructor
-signature, same forward signature and return tuple, same state_dict keys."""
+"""MultiModalEncoder -- drop-in for the reference's model/MMEncoder.py:205-276 (`temporal: "encoding"` or `"embedding"`, `aggregation:
+"avg"` or `"max"`, do_norm either way; one or more modalities), executed by hand-written gfx950 kernels (engine/encoder.py:
+EncoderEngine).  Same constructor signature, same forward signature and return tuple, same state_dict keys for every combination."""
 from typing import List, Optional
 
 import torch
 import torch.nn as nn
 
 from ..engine import EncoderEngine, ParamSet, memory_len
-from ._params import LinearParams, StackParams, sinusoid_table
+from ._params import LinearParams, NormParams, StackParams, sinusoid_table
 
 
 class TemporalEncoding(nn.Module):
@@ -16,6 +16,15 @@ class TemporalEncoding(nn.Module):
     def __init__(self, d_model=512, max_len=512, device=None):
         super().__init__()
         self.register_buffer("pe", sinusoid_table(max_len, d_model, "encoder", device).unsqueeze(0))
+
+
+class TemporalEmbedding(nn.Module):
+    """Holds `embedding.weight` [max_len, d], the learned table of the MMT paper; nn.Embedding's N(0, 1) initialisation and no `pe`
+    buffer (model/MMEncoder.py:118-160).  The lookup and its dense gradient run in vct_enc_frontend_ex_*."""
+
+    def __init__(self, d_model=512, max_len=512, device=None):
+        super().__init__()
+        self.embedding = nn.Embedding(max_len, d_model, device=device)
 
 
 class ModalEmbedding(nn.Module):
@@ -28,7 +37,7 @@ class ModalEmbedding(nn.Module):
         self.modal_emb = nn.Embedding(num_modal * 2 if modal_different else num_modal, d_model, device=device)
 
 
-def grad_ready_order_encoder(prefix, n_layers, n_modal: int = 1):
+def grad_ready_order_encoder(prefix, n_layers, n_modal: int = 1, temporal_type: str = "encoding", do_norm: bool = False):
     names = [prefix + "transformer_encoder.norm.weight", prefix + "transformer_encoder.norm.bias"]
     for l in reversed(range(n_layers)):
         lp = f"{prefix}transformer_encoder.layers.{l}."
@@ -40,6 +49,11 @@ def grad_ready_order_encoder(prefix, n_layers, n_modal: int = 1):
         for i in range(1, n_modal):
             names += [f"{prefix}unify.{i}.weight", f"{prefix}unify.{i}.bias"]
         names.append(prefix + "modal_emb.modal_emb.weight")
+    # the front end's own parameters: written by its backward, i.e. with unify.* in the last gradient bucket
+    if temporal_type == "embedding":
+        names.append(prefix + "temp_emb.embedding.weight")
+    if do_norm:
+        names += [prefix + "norm.weight", prefix + "norm.bias"]
     return names
 
 
@@ -69,18 +83,23 @@ class MultiModalEncoder(nn.Module):
         super().__init__()
         if len(d_feats) < 1:
             raise ValueError("MultiModalEncoder needs at least one feature stream")
-        if global_type != "avg" or temporal_type != "encoding" or do_norm:
-            raise NotImplementedError("accelerated path = aggregation 'avg', temporal 'encoding', do_norm False "
-                                      "(the shipped configs); other encoder variants are out of scope")
-        self.device, self.num_modal, self.do_norm = device, len(d_feats), do_norm
+        if global_type not in ("avg", "max"):
+            raise NotImplementedError(f"aggregation {global_type!r}: the accelerated path has 'avg' and 'max' (the GRU aggregations "
+                                      "are out of scope)")
+        if temporal_type not in ("encoding", "embedding"):      # (the reference takes any other string as 'encoding': say so instead)
+            raise ValueError(f"temporal {temporal_type!r}: 'encoding' or 'embedding'")
+        self.device, self.num_modal, self.do_norm = device, len(d_feats), bool(do_norm)
         self.cfg = dict(d=d_model, nhead=nhead, ff=dim_feedforward, layers=num_encoder_layers, dropout=float(dropout),
-                        activation=activation, n_modal=len(d_feats), modal_different=bool(modal_different))
+                        activation=activation, n_modal=len(d_feats), modal_different=bool(modal_different),
+                        global_type=global_type, temporal_type=temporal_type, do_norm=bool(do_norm))
         self.compute_dtype = compute_dtype
         self.unify = nn.ModuleList([LinearParams(e, d_model, device) for e in d_feats])
-        self.temp_emb = TemporalEncoding(d_model, device=device)
+        self.temp_emb = (TemporalEmbedding if temporal_type == "embedding" else TemporalEncoding)(d_model, device=device)
         if self.num_modal > 1:        # (a single modality has no modal embedding, MMEncoder.py:232)
             self.modal_emb = ModalEmbedding(self.num_modal, d_model, modal_different, device)
         self.transformer_encoder = StackParams(d_model, dim_feedforward, num_encoder_layers, False, device)
+        if self.do_norm:              # LayerNorm (+ Dropout) on the stack input (MMEncoder.py:240-242)
+            self.norm = NormParams(d_model, device)
         self._ps: Optional[ParamSet] = None   # set by the owner (MMT4Caption) or lazily for standalone use
         self._prefix = ""
         self._eng: Optional[EncoderEngine] = None
@@ -96,13 +115,13 @@ class MultiModalEncoder(nn.Module):
                 self._rebuild()
         elif self._ps is None or not self._ps.intact():
             named = dict(self.named_parameters())
-            order = grad_ready_order_encoder("", self.cfg["layers"], self.num_modal)
+            order = grad_ready_order_encoder("", self.cfg["layers"], self.num_modal, self.cfg["temporal_type"], self.do_norm)
             dev = next(self.parameters()).device
             self._ps = ParamSet([(n, named[n]) for n in order], dev, self.compute_dtype)
             self._prefix, self._eng = "", None
             self._seed = torch.tensor([torch.initial_seed() & 0x7FFFFFFF], dtype=torch.int32, device=dev)
         if self._eng is None:
-            self._eng = EncoderEngine(self._ps, self._prefix, self.cfg, self._seed, self.temp_emb.pe)
+            self._eng = EncoderEngine(self._ps, self._prefix, self.cfg, self._seed, getattr(self.temp_emb, "pe", None))
         return self._eng
 
     # ---- reference API ---------------------------------------------------------------------------

@@ -87,7 +87,8 @@ class MMT4Caption(nn.Module):
     def _build_flat(self):
         named = dict(self.named_parameters())
         order = (grad_ready_order_decoder("cap_decoder.", self.cap_decoder.cfg["layers"]) +
-                 grad_ready_order_encoder("video_encoder.", self.video_encoder.cfg["layers"], self.video_encoder.num_modal))
+                 grad_ready_order_encoder("video_encoder.", self.video_encoder.cfg["layers"], self.video_encoder.num_modal,
+                                          self.video_encoder.cfg["temporal_type"], self.video_encoder.do_norm))
         order += [n for n in named if n not in set(order)]   # matching.* (not on the caption path)
         dev = named[order[0]].device
         self._ps = ParamSet([(n, named[n]) for n in order], dev, self.compute_dtype, no_shadow=("cap_decoder.tgt_to_emb.weight",))

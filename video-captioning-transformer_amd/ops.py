@@ -404,6 +404,66 @@ def mm_frontend_bwd(dx, dus, d_modal, labels, B, Ts):
     return dus
 
 
+def _fx_desc(dtype, B, d, Ts, agg, temp, emb_w, tidx, modal_w, labels, norm):
+    """The part of vct_enc_frontend_ex_desc both directions share.  agg 'avg' | 'max'; temporal source: temp fp32 [S, d] (fixed table)
+    or emb_w fp32 [rows, d] with tidx int32 [S] (learned); modal_w / labels: None with one stream; norm: None or the dict of
+    enc_frontend_ex_fwd."""
+    n, S = len(Ts), sum(t + 1 for t in Ts)
+    if not 1 <= n <= L.MM_MAX_MODAL:
+        raise ValueError(f"encoder front end: 1..{L.MM_MAX_MODAL} feature streams, got {n}")
+    if (temp is None) == (tidx is None):
+        raise ValueError("encoder front end: exactly one temporal source (the fixed table, or the embedding weight with its row indices)")
+    if tidx is not None and (tidx.dtype != torch.int32 or tidx.numel() != S):
+        raise ValueError("encoder front end: tidx must be int32 [sum(T_i + 1)]")
+    if n >= 2 and (labels is None or labels.dtype != torch.int32 or labels.numel() != S):
+        raise ValueError("encoder front end: labels must be int32 [sum(T_i + 1)]")
+    desc = L.EncFrontendExDesc()
+    desc.dtype, desc.n, desc.B, desc.d, desc.agg = L.dtype_code(dtype), n, B, d, L.AGG[agg]
+    for i, t in enumerate(Ts):
+        desc.T[i] = int(t)
+    if tidx is not None:
+        desc.temporal, desc.tidx, desc.emb_w, desc.emb_rows = L.TEMPORAL["embedding"], tidx.data_ptr(), L.ptr(emb_w), emb_w.shape[0]
+    else:
+        desc.temporal, desc.temp = L.TEMPORAL["encoding"], temp.data_ptr()
+    if n >= 2:
+        desc.labels, desc.modal_w, desc.n_labels = labels.data_ptr(), L.ptr(modal_w), modal_w.shape[0]
+    if norm is not None:
+        s, site, p = _drop(norm.get("dropout"))
+        desc.norm, desc.gamma, desc.beta, desc.mean, desc.rstd = 1, norm["gamma"].data_ptr(), L.ptr(norm.get("beta")), \
+            norm["mean"].data_ptr(), norm["rstd"].data_ptr()
+        desc.seed, desc.site, desc.p_drop = s, site, p
+    return desc
+
+
+def enc_frontend_ex_fwd(us, masks, x0, key_pad, B, Ts, *, agg="avg", temp=None, emb_w=None, tidx=None, modal_w=None, labels=None,
+                        norm=None):
+    """Encoder front end with every `mme` option (include/vct_hip.h, vct_enc_frontend_ex_fwd), n >= 1 streams: us[i] [B*T_i, d],
+    masks[i] uint8 [B, T_i] or None -> x0 [B*S, d], key_pad uint8 [B, S] (or None).  norm: None, or dict(gamma, beta fp32 [d],
+    mean, rstd fp32 [B*S] (written), dropout = (seed, site, p) or None): x0 = dropout(LayerNorm(pre))."""
+    desc = _fx_desc(x0.dtype, B, x0.shape[-1], Ts, agg, temp, emb_w, tidx, modal_w, labels, norm)
+    for i, u in enumerate(us):
+        desc.u[i] = u.data_ptr()
+        desc.mask[i] = L.ptr(masks[i]) if masks is not None else 0
+    desc.x0, desc.key_pad = x0.data_ptr(), L.ptr(key_pad)
+    L.check(L.load().vct_enc_frontend_ex_fwd(L.C.byref(desc), L.stream_ptr()), "vct_enc_frontend_ex_fwd")
+    return x0
+
+
+def enc_frontend_ex_bwd(dx, dus, B, Ts, *, agg="avg", us=None, temp=None, emb_w=None, tidx=None, modal_w=None, labels=None,
+                        d_modal=None, d_emb=None, norm=None, dpre=None, param_ws=None):
+    """Backward of enc_frontend_ex_fwd: dus[i] [B*T_i, d] <- dx [B*S, d]; d_modal fp32 [n_labels, d] (n >= 2) and d_emb fp32
+    [rows, d] (learned temporal) are WRITTEN.  us: the forward's unify outputs (agg 'max' or norm).  norm: the forward's dict
+    (gamma, mean, rstd, dropout); then dpre fp32 [B*S, d] and param_ws fp32 [B*n*2*d] receive the pre-norm gradient and the
+    norm-parameter partials (ln_param_finalize_batched with B*n rows sums them)."""
+    desc = _fx_desc(dx.dtype, B, dx.shape[-1], Ts, agg, temp, emb_w, tidx, modal_w, labels, norm)
+    for i, du in enumerate(dus):
+        desc.du[i] = du.data_ptr()
+        desc.u[i] = us[i].data_ptr() if us is not None else 0
+    desc.dx, desc.d_modal, desc.d_emb, desc.dpre, desc.param_ws = dx.data_ptr(), L.ptr(d_modal), L.ptr(d_emb), L.ptr(dpre), L.ptr(param_ws)
+    L.check(L.load().vct_enc_frontend_ex_bwd(L.C.byref(desc), L.stream_ptr()), "vct_enc_frontend_ex_bwd")
+    return dus
+
+
 def embed_fwd(ids, S, table, pos, x, dropout: Drop = None):
     """ids: int64 [B, S_total] (row stride = ids.stride(0)); uses the first S columns of each row."""
     B = ids.shape[0]
