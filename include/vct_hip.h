@@ -156,6 +156,32 @@ int vct_attn_fwd(const vct_attn_desc* d, void* stream);
 int vct_attn_bwd(const vct_attn_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Head-averaged attention map: W[b, i, j] = (1/H) * sum_h softmax_j(q[b,i,h] . k[b,j,h] / sqrt(hd) + mask)[j], fp32 [B, Lq, Lk].
+ * One wave per (batch, 16-query tile) walks the heads in ascending order and sums the probabilities in fp32 registers (no atomics,
+ * no second pass: two runs are bitwise equal); scores, masks and exponentials are the forward's (csrc/vct_attn_core.h), so a map
+ * is the probability vct_attn_fwd multiplied V with at p_drop = 0.  A fully masked row is all zero.  No V, no dropout, no O.
+ * replaces: nn.MultiheadAttention's need_weights=True, average_attn_weights=True return value (torch nn/functional.py:6572-6589)
+ * as VisTransformerDecoderLayer keeps it (CapDecoder.py:112-113) and as predict_video.py's patched layers record it per generated
+ * token (predict_video.py:63-64).
+ *   q, k, masks, dtype, limits and alignment: as vct_attn_desc (Lq, Lk <= 64, hd <= 128; q and k 16-byte aligned).
+ *   w: fp32, row i of batch b at w + b * w_bs + i * ldw (ldw >= Lk; w_bs 0 = dense: Lq * ldw) -- a decode step writes row t-1 of a
+ *   [B, layers, Lmax-1, Te] buffer with Lq = 1, w_bs = layers * (Lmax-1) * Te.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct vct_attn_weights_desc {
+  int32_t dtype;
+  int32_t B, H, Lq, Lk, hd;
+  int32_t causal;
+  int32_t key_pad_shift;
+  const void* q; int64_t ldq;
+  const void* k; int64_t ldk;
+  float* w; int64_t ldw;
+  const uint8_t* key_pad;
+  int64_t q_bs, k_bs, w_bs;          /* batch strides in ELEMENTS (0 = dense) */
+  const int64_t* key_ids; int64_t key_ids_bs; int64_t pad_id;
+} vct_attn_weights_desc;
+int vct_attn_weights(const vct_attn_weights_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Sample-stationary Transformer stack forward (bf16): ONE launch = up to 4 whole encoder / decoder layers (and, with last != 0
  * in the last descriptor, the stack-final LayerNorm); one 512-thread workgroup per SAMPLE keeps that sample's rows in LDS
  * from the first layer's input to the last layer's output and streams the weights from L2 straight into MFMA operand

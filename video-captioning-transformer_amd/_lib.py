@@ -48,6 +48,13 @@ class AttnDesc(C.Structure):
                 ("key_ids", vp), ("key_ids_bs", i64), ("pad_id", i64)]
 
 
+class AttnWeightsDesc(C.Structure):
+    """include/vct_hip.h, vct_attn_weights_desc: head-averaged attention map."""
+    _fields_ = [("dtype", i32), ("B", i32), ("H", i32), ("Lq", i32), ("Lk", i32), ("hd", i32), ("causal", i32),
+                ("key_pad_shift", i32), ("q", vp), ("ldq", i64), ("k", vp), ("ldk", i64), ("w", vp), ("ldw", i64),
+                ("key_pad", vp), ("q_bs", i64), ("k_bs", i64), ("w_bs", i64), ("key_ids", vp), ("key_ids_bs", i64), ("pad_id", i64)]
+
+
 class SsNorm(C.Structure):
     _fields_ = [("gamma", vp), ("beta", vp), ("y", vp), ("mean", vp), ("rstd", vp)]
 
@@ -146,6 +153,7 @@ _SIGS = {
     "vct_gemm_grouped_workspace_bytes": (i64, [C.POINTER(GemmDesc), i32, i32]),
     "vct_attn_fwd": (C.c_int, [C.POINTER(AttnDesc), vp]),
     "vct_attn_bwd": (C.c_int, [C.POINTER(AttnDesc), vp]),
+    "vct_attn_weights": (C.c_int, [C.POINTER(AttnWeightsDesc), vp]),
     "vct_layer_ss_supported": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "vct_layer_ss_stream_chunks": (i64, [C.c_int, C.c_int]),
     "vct_ss_pack": (C.c_int, [C.POINTER(SsPackSeg), C.c_int, vp, vp]),

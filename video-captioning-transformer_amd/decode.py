@@ -48,29 +48,42 @@ def greedy_decode_ids_reference_algorithm(model, feats: torch.Tensor, mask, max_
     return ys[:, :t].clone()
 
 
-def _session(model, dec, B, Te, max_len) -> DecodeState:
+def _session(model, dec, B, Te, max_len, return_attn: bool = False) -> DecodeState:
     cache = model.__dict__.setdefault("_decode_sessions", {})
-    key = (B, Te, max_len, dec.dt)
+    # (graphs bake pointers and launches: a session that returns attention maps is another session, and one without never
+    # captures the extra launches)
+    key = (B, Te, max_len, dec.dt) + (("attn",) if return_attn else ())
     st = cache.get(key)
     if st is None:
         if len(cache) > 3:
             cache.clear()
-        st = cache[key] = DecodeState(dec, B, Te, max_len)
+        st = cache[key] = DecodeState(dec, B, Te, max_len, return_attn=return_attn)
     return st
+
+
+def _no_beam_attn(return_attn: bool):
+    if return_attn:
+        raise ValueError("return_attn is not supported by beam search: the maps would have to follow the beams' parent "
+                         "back-track; use greedy_decode_ids(return_attn=True)")
 
 
 @torch.no_grad()
 def greedy_decode_ids(model, feats: torch.Tensor, mask, max_len: int = 30, use_graphs: bool = True,
-                      sync_every: int = 4, lookahead: int = 3) -> torch.Tensor:
-    """Returns ys int64 [B, <= max_len], identical to the reference loop's id matrix.
+                      sync_every: int = 4, lookahead: int = 3, return_attn: bool = False):
+    """Returns ys int64 [B, <= max_len], identical to the reference loop's id matrix.  return_attn: (ys, maps) with maps fp32
+    [B, layers, ys.shape[1] - 1, Te]: row t-1 of layer l = the head-averaged cross-attention of the token consumed at step t
+    (what predict_video.py --vis_attn records, predict_video.py:43-79); rows of a caption that has already ended hold what the
+    step computed, as in the reference.
 
     The host never waits for the step it has just launched: it keeps `lookahead` token steps queued and, every `sync_every`
     steps, reads the device-side "every caption has ended at step s" word as of the step that left the queue (a copy on a second
     stream issued once the host has seen THAT step's event complete) -- the reference syncs on every token (`.tolist()`, MMT4Caption.py:168).  A
     caption batch that ends at step s therefore costs at most s + lookahead steps; the id matrix is truncated at s."""
     dec = model.cap_decoder._engine()
-    st = _session(model, dec, _first(feats).shape[0], memory_len(feats), max_len)
+    st = _session(model, dec, _first(feats).shape[0], memory_len(feats), max_len, return_attn)
     stop = _run_session(model, st, feats, mask, max_len, use_graphs, sync_every, lookahead, dec.decode_begin, dec.decode_step)
+    if return_attn:
+        return st.ys[:, :stop + 1].clone(), st.attn_maps[:, :, :stop].clone()
     return st.ys[:, :stop + 1].clone()
 
 
@@ -154,19 +167,20 @@ def _run_session(model, st, feats, mask, max_len, use_graphs, sync_every, lookah
 
 
 @torch.no_grad()
-def teacher_forced_next_ids(model, feats: torch.Tensor, mask, prefix_ids: torch.Tensor, steps: int, return_logits: bool = False):
+def teacher_forced_next_ids(model, feats: torch.Tensor, mask, prefix_ids: torch.Tensor, steps: int, return_logits: bool = False,
+                            return_attn: bool = False):
     """The KV-cache token step of greedy_decode_ids (same kernels, same cache) with the CONSUMED token of every step forced to
     `prefix_ids[:, t - 1]` instead of the step's own previous prediction: returns the predicted next ids [B, steps]
     (column t - 1 = arg-max after consuming prefix_ids[:, :t]).  This is CapDecoder.decode_word + torch.max of the reference
     (CapDecoder.py:62-79, MMT4Caption.py:164-165) evaluated along a given caption -- what a low-precision path can be held
     to where free-running ids would diverge after the first unresolvable logit gap.  return_logits: also the fp32 logits
-    [B, steps, V] of every step."""
+    [B, steps, V] of every step.  return_attn: also (last) the cross-attention maps fp32 [B, layers, steps, Te] of greedy_decode_ids."""
     pre = model.cap_preprocessor
     model._ps.refresh_shadow()
     model._ps.refresh_lazy_transposed()
     enc, dec = model.video_encoder._engine(), model.cap_decoder._engine()
     B, dev = _first(feats).shape[0], _first(feats).device
-    st = DecodeState(dec, B, memory_len(feats), steps + 1)
+    st = DecodeState(dec, B, memory_len(feats), steps + 1, return_attn=return_attn)
     dec.decode_begin(st, enc.forward(feats, mask, False), pre.start_id, pre.pad_id)
     out = torch.empty(B, steps, dtype=torch.long, device=dev)
     logits = torch.empty(B, steps, dec.V, dtype=torch.float32, device=dev) if return_logits else None
@@ -176,7 +190,10 @@ def teacher_forced_next_ids(model, feats: torch.Tensor, mask, prefix_ids: torch.
         out[:, t - 1] = st.ys[:, t]
         if return_logits:
             logits[:, t - 1] = st.last_logits[:, :dec.V].float()
-    return (out, logits) if return_logits else out
+    res = (out, logits) if return_logits else (out,)
+    if return_attn:
+        res = res + (st.attn_maps[:, :, :steps].clone(),)
+    return res if len(res) > 1 else res[0]
 
 
 def _beam_session(model, dec, B, K, Te, max_len) -> BeamDecodeState:
@@ -207,7 +224,8 @@ def _beam_finish(ids: torch.Tensor, scores: torch.Tensor, B: int, K: int, end_id
 
 @torch.no_grad()
 def beam_decode_ids(model, feats: torch.Tensor, mask, beam_size: int, max_len: int = 30, length_penalty: float = 1.0,
-                    use_graphs: bool = True, return_all: bool = False, sync_every: int = 4, lookahead: int = 3):
+                    use_graphs: bool = True, return_all: bool = False, sync_every: int = 4, lookahead: int = 3,
+                    return_attn: bool = False):
     """Beam search on the KV-cached decode step.  Returns the best ids int64 [B, L'] (L' <= max_len), or with return_all
     (ids [B, K, L'], final scores fp32 [B, K]), each video's beams sorted best first.
 
@@ -228,7 +246,8 @@ def beam_decode_ids(model, feats: torch.Tensor, mask, beam_size: int, max_len: i
 
     One captured hipGraph per position (it bakes the ping-pong side of the cache), the begin graph and the stop polling of
     greedy_decode_ids.  The batch-1 block step is greedy-only: beams run on the gemv (B*K = 1), fused (bf16, 2..256 rows) or
-    generic batched step."""
+    generic batched step.  return_attn=True raises ValueError (attention maps are a greedy-decode feature)."""
+    _no_beam_attn(return_attn)
     pre = model.cap_preprocessor
     dec = model.cap_decoder._engine()
     K = int(beam_size)
@@ -269,10 +288,11 @@ def _select_ref(vals: torch.Tensor, valid: torch.Tensor, K: int):
 
 @torch.no_grad()
 def beam_decode_ids_reference_algorithm(model, feats: torch.Tensor, mask, beam_size: int, max_len: int = 30,
-                                        length_penalty: float = 1.0, return_all: bool = False):
+                                        length_penalty: float = 1.0, return_all: bool = False, return_attn: bool = False):
     """beam_decode_ids without the KV cache: every step re-runs the whole decoder (dec.decode_word) on the reordered [B*K, t]
     histories and selects on the host in torch by the same rule.  Returns (result as beam_decode_ids, min margin): the smallest
     gap between the K-th and (K+1)-th candidate value over every video and step (where a test may not expect ids to agree)."""
+    _no_beam_attn(return_attn)
     pre = model.cap_preprocessor
     model._ps.refresh_shadow()
     model._ps.refresh_lazy_transposed()

@@ -21,5 +21,5 @@ from .encoder import EncoderEngine
 from .decode_step import (BeamDecodeState, DecodeState, _beam_stage, _decoder_beam_begin, _decoder_beam_step,
                           _decoder_block_decode_ok, _decoder_decode_begin, _decoder_decode_step, _decoder_decode_step_any,
                           _decoder_decode_step_block, _decoder_decode_step_fused, _decoder_decode_step_small,
-                          _decoder_fused_decode_ok, _decoder_small_decode_ok, _greedy_stage)
+                          _decoder_fused_decode_ok, _decoder_small_decode_ok, _greedy_stage, decode_step_variant)
 from .decoder import DecoderEngine

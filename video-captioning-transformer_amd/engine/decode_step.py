@@ -11,9 +11,12 @@ class DecodeState:
     cache [B, Lmax, 3d] (packed q | k | v of every consumed token), per-layer cross-attention K/V of the memory (computed once), step temporaries
     and the hipGraphs of the per-token step (one per position; every kernel argument is baked)."""
 
-    def __init__(self, eng: "DecoderEngine", Bn: int, Te: int, Lmax: int):
+    def __init__(self, eng: "DecoderEngine", Bn: int, Te: int, Lmax: int, return_attn: bool = False):
         d, L, dt, dev = eng.cfg["d"], eng.cfg["layers"], eng.dt, eng.dev
         self.B, self.Te, self.Lmax = Bn, Te, Lmax
+        # return_attn: row t-1 of layer l = the head-averaged cross-attention of the token consumed at step t (predict_video.py:63-64);
+        # None = the step issues no map launch at all
+        self.attn_maps = torch.zeros(Bn, L, max(Lmax - 1, 1), Te, dtype=torch.float32, device=dev) if return_attn else None
         self.ys = torch.zeros(Bn, Lmax, dtype=torch.long, device=dev)
         self.ended = torch.zeros(Bn, dtype=torch.bool, device=dev)
         self.ended_count = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -37,6 +40,14 @@ def _finish_step(eng, st: DecodeState, logits: torch.Tensor, t: int, end_id: int
     """The end of every step variant that takes `select`: publish the step's logits, run the selection stage (None = greedy)."""
     st.last_logits = logits          # [B, Vp] of this step (decode.teacher_forced_next_ids reads it)
     (select or _greedy_stage)(eng, st, logits, t, end_id)
+
+
+def _attn_map_row(eng, st: DecodeState, l: int, t: int, qc: torch.Tensor):
+    """Sessions that return attention maps: one vct_attn_weights launch per layer once the cross-attention query of the consumed
+    token exists (Lq = 1, keys = the cached K projection of the memory) -> row t-1 of layer l."""
+    if st.attn_maps is not None:
+        d = eng.cfg["d"]
+        ops.attn_weights(qc, st.kv_cross[l][:, :d], st.attn_maps[:, l, t - 1:t, :], st.B, eng.cfg["nhead"], 1, st.Te)
 
 
 def _decoder_decode_begin(eng, st: DecodeState, mem: torch.Tensor, start_id: int, pad_id: int):
@@ -80,6 +91,7 @@ def _decoder_decode_step(eng, st: DecodeState, t: int, end_id: int, select=None)
         ops.gemm(x1, eng.W(ca + "in_proj_weight")[:d], qc, bias=eng.F(ca + "in_proj_bias")[:d], workspace=ws)
         oc = b.get(tag + "oc", (Bn, d), eng.dt)
         ops.attn_fwd(qc, st.kv_cross[l][:, :d], st.kv_cross[l][:, d:], oc, Bn, H, 1, Te)
+        _attn_map_row(eng, st, l, t, qc)
         c = b.get(tag + "c", (Bn, d), eng.dt)
         ops.gemm(oc, eng.W(ca + "out_proj.weight"), c, bias=eng.F(ca + "out_proj.bias"), workspace=ws)
         x2 = eng._ln_fwd(b, tag + "n2.", lp + "norm2.", c, x1, None)
@@ -145,6 +157,7 @@ def _decoder_decode_step_small(eng, st: DecodeState, t: int, end_id: int, select
         kvc = st.kv_cross[l]                                               # [B * Te, 2d]
         ops.decode_gemv(eng.W(ca + "out_proj.weight"), s2, B, bias=eng.F(ca + "out_proj.bias"), pro="cross_attn",
                         attn=(qc, kvc[:, :d], kvc[:, d:], 2 * d, Te * 2 * d, H, Te), res=x1)
+        _attn_map_row(eng, st, l, t, qc)           # (before the next layer overwrites the shared query vector)
         # x2 = norm2(s2); feed-forward
         ops.decode_gemv(eng.W(lp + "linear1.weight"), h, B, bias=eng.F(lp + "linear1.bias"), pro="ln", x_in=s2,
                         ln1=(eng.F(lp + "norm2.weight"), eng.F(lp + "norm2.bias")), act=eng.cfg["activation"], x_out=x2)
@@ -160,6 +173,8 @@ def _decoder_block_decode_ok(eng, st: DecodeState) -> bool:
     """The batch-1 step with one launch per layer BLOCK (ops.decode_block): bf16, d = 512 with head_dim 64, ff <= 2048, <= 64 positions
     (vct_decode_block_supported is the authority: anything else falls through to the gemv / skinny / batched steps)."""
     d, ff, H = eng.cfg["d"], eng.cfg["ff"], eng.cfg["nhead"]
+    if st.attn_maps is not None:      # the block step keeps its cross-attention query inside the kernel: the gemv / generic step takes over
+        return False
     return (eng.block_decode and st.B == 1 and eng.dev.type == "cuda" and st.Lmax <= 64 and st.Te <= 64
             and ops.decode_block_supported(eng.dt, d, H, ff, min(st.Lmax, 64)))
 
@@ -246,6 +261,7 @@ def _decoder_decode_step_fused(eng, st: DecodeState, t: int, end_id: int, select
                           x_norm=x1, bias=eng.F(ca + "in_proj_bias")[:d])
         oc = b.get(tag + "oc", (Bn, d), eng.dt)
         ops.attn_fwd(qc, st.kv_cross[l][:, :d], st.kv_cross[l][:, d:], oc, Bn, H, 1, Te)
+        _attn_map_row(eng, st, l, t, qc)
         s2 = b.get(tag + "s2", (Bn, d), f32)
         ops.decode_linear(eng.W(ca + "out_proj.weight"), s2, x=oc, bias=eng.F(ca + "out_proj.bias"), res=x1)
         x2 = b.get(tag + "x2", (Bn, d), f32)
@@ -262,16 +278,23 @@ def _decoder_decode_step_fused(eng, st: DecodeState, t: int, end_id: int, select
     _finish_step(eng, st, logits, t, end_id, select)
 
 
+def decode_step_variant(eng, st: DecodeState, select=None) -> str:
+    """The step variant of this session, 'block' | 'gemv' | 'fused' | 'generic': what _decoder_decode_step_any dispatches on."""
+    if select is None and _decoder_block_decode_ok(eng, st):
+        return "block"
+    if _decoder_small_decode_ok(eng, st):
+        return "gemv"
+    return "fused" if _decoder_fused_decode_ok(eng, st) else "generic"
+
+
 def _decoder_decode_step_any(eng, st: DecodeState, t: int, end_id: int, select=None):
     """select: the selection stage at the end of the step, (engine, state, logits, t, end_id) -> None; None = greedy.  The batch-1
     block step fuses greedy selection into its generator launch: any other stage takes the gemv / fused / generic step."""
-    if select is None and _decoder_block_decode_ok(eng, st):
+    variant = decode_step_variant(eng, st, select)
+    if variant == "block":
         return _decoder_decode_step_block(eng, st, t, end_id)
-    if _decoder_small_decode_ok(eng, st):
-        return _decoder_decode_step_small(eng, st, t, end_id, select)
-    if _decoder_fused_decode_ok(eng, st):
-        return _decoder_decode_step_fused(eng, st, t, end_id, select)
-    return _decoder_decode_step(eng, st, t, end_id, select)
+    step = {"gemv": _decoder_decode_step_small, "fused": _decoder_decode_step_fused, "generic": _decoder_decode_step}[variant]
+    return step(eng, st, t, end_id, select)
 
 
 class BeamDecodeState(DecodeState):
@@ -284,7 +307,7 @@ class BeamDecodeState(DecodeState):
     slot is finished."""
 
     def __init__(self, eng: "DecoderEngine", Bv: int, K: int, Te: int, Lmax: int):
-        super().__init__(eng, Bv * K, Te, Lmax)
+        super().__init__(eng, Bv * K, Te, Lmax)      # (no attention maps: they would have to follow the parent back-track)
         d, L, dt, dev = eng.cfg["d"], eng.cfg["layers"], eng.dt, eng.dev
         M = Bv * K
         self.Bv, self.K = Bv, K

@@ -26,6 +26,7 @@ class DecoderEngine(_StackBase):
     fused_decode = True             # A/B switch: LayerNorms folded into the skinny projections (2 <= batch <= 256, bf16)
     block_decode = os.environ.get("VCT_BLOCK_DECODE", "1") != "0"   # A/B switch: 3 launches per layer at batch 1 (bf16)
     small_batch_decode = True       # A/B switch: weight-streaming GEMV step for batch <= 4
+    attn_maps = False               # set per ENGINE by CapDecoder(custom_decoder_type=...): every forward also leaves the cross-attention maps
 
     def __init__(self, ps, prefix, cfg, seed, pos_buffer: torch.Tensor):
         super().__init__(ps, prefix, cfg, seed)
@@ -38,6 +39,7 @@ class DecoderEngine(_StackBase):
         ls = range(cfg["layers"])      # per layer: parameter prefix, buffer tag, dropout site base (lists for _stack_ss; the unfused loops index them)
         self.lps, self.tags, self.sites = [f"decoder.layers.{l}." for l in ls], [f"L{l}." for l in ls], [DEC_SITE + 16 * l for l in ls]
         self._wgt = None     # W_g^T of the current forward when the vocabulary dX runs in its NT form (gen_dx_nt), else None
+        self.last_attn_maps = None     # attn_maps: fp32 [B, S-1, Te] per layer of the last forward (views of static buffers)
 
     def _ws_grew(self):
         self.ps.ctx.generation += 1      # recordings that baked the outgrown id workspace are dropped by their owners
@@ -147,7 +149,20 @@ class DecoderEngine(_StackBase):
                      b.get("row_ws", (2 * M + 2,), torch.float32))
         ops.tap("loss", 1)
         b.t["dlogits_used"] = dlogits
+        if self.attn_maps:
+            self.last_attn_maps = self._cross_attn_maps(b, Bn, Sd, Te)
         return loss, (logits if want_logits else None)
+
+    def _cross_attn_maps(self, b, Bn, Sd, Te):
+        """The head-averaged cross-attention probabilities of every layer, from the query and K projections the forward saved (the
+        sample-stationary stack's cq / ckv, the unfused schedule's ca. buffers): one vct_attn_weights launch per layer behind the loss,
+        nothing recomputed but the scores.  In training these are the probabilities BEFORE dropout."""
+        d, H = self.cfg["d"], self.cfg["nhead"]
+        maps = []
+        for tag in self.tags:
+            w = b.get(tag + "ca.w", (Bn, Sd, Te), torch.float32)
+            maps.append(ops.attn_weights(b.t[tag + "ca.q"], b.t[tag + "ca.kv"][:, :d], w, Bn, H, Sd, Te))
+        return maps
 
     def decode_word(self, mem: torch.Tensor, Bn: int, Te: int, ys: torch.Tensor) -> torch.Tensor:
         """Reference algorithm of CapDecoder.decode_word (CapDecoder.py:62-79): re-run the decoder over

@@ -15,29 +15,47 @@ def _strip_special(s: str) -> str:
 
 
 @torch.no_grad()
-def _decode(model, feats, masks, max_len, beam_size):
+def _decode(model, feats, masks, max_len, beam_size, return_attn=False):
     if beam_size is None:
-        return model.greedy_decode(feats, masks, max_len=max_len)
-    return model.beam_decode(feats, masks, beam_size=beam_size, max_len=max_len)
+        return model.greedy_decode(feats, masks, max_len=max_len, return_attn=return_attn)
+    return model.beam_decode(feats, masks, beam_size=beam_size, max_len=max_len, return_attn=return_attn)
+
+
+def average_attention(maps: torch.Tensor, length: Optional[int] = None) -> torch.Tensor:
+    """The matrix predict_video.visualize plots (predict_video.py:126-142): the mean over layers of one caption's maps
+    [layers, steps, Te] -> [steps, Te] (a batch [B, layers, steps, Te] -> [B, steps, Te]), cut to the first `length` generated
+    tokens.  Plotting itself is left to the caller."""
+    if maps.dim() not in (3, 4):
+        raise ValueError("maps: [layers, steps, Te] of one caption or [B, layers, steps, Te]")
+    avg = maps.float().mean(dim=maps.dim() - 3)
+    return avg if length is None else avg[..., :int(length), :]
 
 
 @torch.no_grad()
 def v2t_batch(model, video_feats: Sequence[torch.Tensor], video_masks: Optional[Sequence[torch.Tensor]], max_len: int = 30,
-              beam_size: Optional[int] = None) -> List[str]:
+              beam_size: Optional[int] = None, return_attn: bool = False):
     """eval.py:126-145: video_feats = list (one per modality) of [B, T, E]; masks = list of bool [B, T] or None.
-    beam_size: None = greedy (the reference's only mode), else beam search with that many beams (MMT4Caption.beam_decode)."""
+    beam_size: None = greedy (the reference's only mode), else beam search with that many beams (MMT4Caption.beam_decode).
+    return_attn (greedy only): (captions, cross-attention maps fp32 [B, layers, steps, Te]) -- MMT4Caption.greedy_decode_ids."""
     model.eval()
     dev = model.device
     video_feats = [f.to(dev, non_blocking=True) for f in video_feats]
     video_masks = [m.to(dev, non_blocking=True) for m in video_masks] if video_masks is not None else None
+    if return_attn:
+        caps, maps = _decode(model, video_feats, video_masks, max_len, beam_size, True)
+        return [_strip_special(r) for r in caps], maps
     return [_strip_special(r) for r in _decode(model, video_feats, video_masks, max_len, beam_size)]
 
 
 @torch.no_grad()
-def v2t_single(model, video_feat: Sequence[torch.Tensor], max_len: int = 30, beam_size: Optional[int] = None) -> str:
-    """train.py:194-203: one video (list of [T, E] per modality), no mask."""
+def v2t_single(model, video_feat: Sequence[torch.Tensor], max_len: int = 30, beam_size: Optional[int] = None,
+               return_attn: bool = False):
+    """train.py:194-203: one video (list of [T, E] per modality), no mask.  return_attn: (caption, maps fp32 [layers, steps, Te])."""
     model.eval()
     feats = [f.unsqueeze(0).to(model.device) for f in video_feat]
+    if return_attn:
+        caps, maps = _decode(model, feats, None, max_len, beam_size, True)
+        return _strip_special(caps[0]), maps[0]
     return _strip_special(_decode(model, feats, None, max_len, beam_size)[0])
 
 

@@ -41,6 +41,7 @@ class _DecoderFn(torch.autograd.Function):
         eng = mod._engine()
         B, Te, d = mem.shape
         loss, logits = eng.forward(mem.reshape(B * Te, d), B, Te, ids, mod.training, want_logits=want_logits)
+        mod._publish_attn(eng)
         ctx.mod, ctx.shape = mod, (B, Te, d)
         out_logits = logits[:, :eng.V].reshape(B, ids.shape[1] - 1, eng.V) if want_logits else loss.new_zeros(())
         ctx.mark_non_differentiable(out_logits)
@@ -63,8 +64,9 @@ class CapDecoder(nn.Module):
                  custom_decoder_type: Optional[str] = None, activation="gelu", device=torch.device("cuda"),
                  compute_dtype: torch.dtype = torch.bfloat16):
         super().__init__()
-        if custom_decoder_type is not None:
-            raise NotImplementedError("Vis* decoder layers (attention-map visualisation) are outside the accelerated path")
+        # any non-None type builds the reference's VisTransformerDecoder (CapDecoder.py:17-24): the stock layers' parameters and
+        # state_dict keys, plus `attn_weights` (one head-averaged cross-attention map [B, S-1, Te] per layer) after every forward
+        self.custom_decoder_type = custom_decoder_type
         self.device, self.compute_dtype = device, compute_dtype
         self.cfg = dict(d=embed_dim, nhead=nhead, ff=dim_feedforward, layers=num_layers, dropout=float(dropout),
                         activation=activation, vocab=vocab_size, pad_id=pad_id, sce_loss_alpha=float(sce_loss_alpha))
@@ -95,7 +97,14 @@ class CapDecoder(nn.Module):
             self._seed = torch.tensor([torch.initial_seed() & 0x7FFFFFFF], dtype=torch.int32, device=dev)
         if self._eng is None:
             self._eng = DecoderEngine(self._ps, self._prefix, self.cfg, self._seed, self.positional_encoding.pos_embedding)
+            self._eng.attn_maps = self.custom_decoder_type is not None
         return self._eng
+
+    def _publish_attn(self, eng):
+        """After a forward of a Vis decoder: cap_decoder.attn_weights (CapDecoder.py:53-54) -- fp32 [B, S-1, Te] per layer, views of
+        the engine's static buffers (a replayed launch list / hipGraph of the step refreshes them in place)."""
+        if eng.attn_maps:
+            self.attn_weights = eng.last_attn_maps
 
     def _scale_grads_if_needed(self, gloss):
         """The kernels produce gradients for d(loss) = 1; apply the incoming scalar to this module's

@@ -167,6 +167,7 @@ class MMT4Caption(nn.Module):
             dec.forward_prefix(B, Te, ids, training)
         mem = enc.forward(feats, mask, training)
         loss, logits = dec.forward(mem, B, Te, ids, training, want_logits=want_logits)
+        self.cap_decoder._publish_attn(dec)
         return loss, logits
 
     @property
@@ -276,7 +277,11 @@ class MMT4Caption(nn.Module):
 
     @torch.no_grad()
     def greedy_decode(self, video_feat: List[torch.Tensor], video_masks: Optional[List[torch.Tensor]] = None,
-                      max_len: int = 30) -> List[str]:
+                      max_len: int = 30, return_attn: bool = False):
+        """return_attn: (captions, maps fp32 [B, layers, steps, Te]) -- see greedy_decode_ids."""
+        if return_attn:
+            ys, maps = self.greedy_decode_ids(video_feat, video_masks, max_len, return_attn=True)
+            return self._ids_to_captions(ys), maps
         return self._ids_to_captions(self.greedy_decode_ids(video_feat, video_masks, max_len))
 
     def _ids_to_captions(self, ys: torch.Tensor) -> List[str]:
@@ -295,32 +300,42 @@ class MMT4Caption(nn.Module):
 
     @torch.no_grad()
     def greedy_decode_ids(self, video_feat, video_masks=None, max_len: int = 30, kv_cache: bool = True,
-                          use_graphs: bool = True) -> torch.Tensor:
+                          use_graphs: bool = True, return_attn: bool = False):
         """The id matrix ys [B, <=max_len] of MMT4Caption.greedy_decode (MMT4Caption.py:159-172).
-        kv_cache=False runs the reference's O(L^2) algorithm (full decoder re-run per token)."""
+        kv_cache=False runs the reference's O(L^2) algorithm (full decoder re-run per token).
+        return_attn (KV cache only; any model, with or without caption_decoder.layer_type): (ys, maps) with maps fp32
+        [B, layers, ys.shape[1] - 1, Te], row t-1 = the head-averaged cross-attention of the token consumed at step t
+        (predict_video.py --vis_attn)."""
+        if return_attn and not kv_cache:
+            raise ValueError("return_attn needs the KV-cached decode (kv_cache=True)")
         was_training = self.training
         self.eval()
         try:
             from .. import decode
             feats, mask = self._video_inputs(video_feat, video_masks)
             if kv_cache:
-                return decode.greedy_decode_ids(self, feats, mask, max_len, use_graphs=use_graphs)
+                return decode.greedy_decode_ids(self, feats, mask, max_len, use_graphs=use_graphs, return_attn=return_attn)
             return decode.greedy_decode_ids_reference_algorithm(self, feats, mask, max_len)
         finally:
             self.train(was_training)
 
     @torch.no_grad()
     def beam_decode(self, video_feat: List[torch.Tensor], video_masks: Optional[List[torch.Tensor]] = None, beam_size: int = 5,
-                    max_len: int = 30, length_penalty: float = 1.0) -> List[str]:
+                    max_len: int = 30, length_penalty: float = 1.0, return_attn: bool = False) -> List[str]:
         """Beam-search captions, one string per video (the reference's beam_decode is `pass`, MMT4Caption.py:186); ids -> text
-        as greedy_decode.  Semantics: decode.beam_decode_ids."""
+        as greedy_decode.  Semantics: decode.beam_decode_ids.  return_attn=True raises ValueError: attention maps would have to
+        follow the beams' parent back-track (greedy decoding returns them)."""
+        from ..decode import _no_beam_attn
+        _no_beam_attn(return_attn)
         return self._ids_to_captions(self.beam_decode_ids(video_feat, video_masks, beam_size, max_len, length_penalty))
 
     @torch.no_grad()
     def beam_decode_ids(self, video_feat, video_masks=None, beam_size: int = 5, max_len: int = 30, length_penalty: float = 1.0,
-                        kv_cache: bool = True, use_graphs: bool = True, return_all: bool = False):
+                        kv_cache: bool = True, use_graphs: bool = True, return_all: bool = False, return_attn: bool = False):
         """The best beam's id matrix [B, <=max_len] (return_all: (ids [B, K, L'], final scores [B, K])) of beam_decode.
         kv_cache=False runs the reference algorithm (full decoder re-run per token, host-side selection)."""
+        from ..decode import _no_beam_attn
+        _no_beam_attn(return_attn)
         was_training = self.training
         self.eval()
         try:

@@ -166,6 +166,23 @@ def attn_fwd(q, k, v, o, B, H, Lq, Lk, causal=False, key_pad=None, dropout: Drop
     return o
 
 
+def attn_weights(q, k, w, B, H, Lq, Lk, causal=False, key_pad=None, kv_batch_stride: int = 0):
+    """w fp32 [B, Lq, Lk] view (last dimension contiguous, any row / batch stride) = mean over the H heads of
+    softmax(q k^T / sqrt(hd) + mask): nn.MultiheadAttention's averaged attention weights (include/vct_hip.h, vct_attn_weights).
+    q: [B*Lq, >=H*hd] view, k: [B*Lk, ..] view, key_pad / kv_batch_stride as attn_fwd."""
+    assert w.dtype == torch.float32 and tuple(w.shape) == (B, Lq, Lk) and w.stride(2) == 1
+    hd = q.shape[1] // H
+    src = _attn_desc(q.dtype, B, H, Lq, Lk, hd, causal, q, k, k, key_pad, None)
+    d = L.AttnWeightsDesc()
+    for f in ("dtype", "B", "H", "Lq", "Lk", "hd", "causal", "key_pad_shift", "q", "ldq", "k", "ldk", "key_pad",
+              "key_ids", "key_ids_bs", "pad_id"):
+        setattr(d, f, getattr(src, f))
+    d.w, d.ldw, d.w_bs = w.data_ptr(), (w.stride(1) if Lq > 1 else Lk), w.stride(0)
+    d.k_bs = kv_batch_stride
+    L.check(L.load().vct_attn_weights(d, L.stream_ptr()), "vct_attn_weights")
+    return w
+
+
 # ---- sample-stationary layer forward (csrc/vct_layer_ss.hip) ---------------------------------------------------------------------
 _ss_ok = {}
 SS_CHUNK = 32768          # bf16 elements per 64-KiB chunk of a packed weight stream

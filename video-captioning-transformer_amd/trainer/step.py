@@ -47,6 +47,9 @@ class CaptionTrainer:
         self._lists = {}
         self._graphs = {}
         self._static = {}                 # per input shape: the static input buffers the recordings read
+        # per input shape, Vis decoders only: the attention-map views that shape's recording writes.  Every shape shares the engine's
+        # grow-only buffers, so the views Python published for the LAST shape it ran have another shape's dimensions
+        self._attn = {}
         self._gen = None                  # the buffer generation (engine.StepContext) the recordings were made at
         if single and model.flat_grads.is_cuda:
             # this trainer (zero_grad implicit, no exchange, no in-place averaging) is the only writer of the gradient buffer
@@ -159,6 +162,7 @@ class CaptionTrainer:
         anything that changes WHAT a step launches, e.g. ops.taps_enable(...)."""
         self._lists.clear()
         self._graphs.clear()
+        self._attn.clear()
 
     def _static_inputs(self, key, feats, mask, ids):
         s = self._static.get(key)
@@ -234,10 +238,14 @@ class CaptionTrainer:
             hit = record(static)
             if hit is not None:
                 cache[key] = hit
+                if self.model.cap_decoder.custom_decoder_type is not None:
+                    self._attn[key] = self.model.cap_decoder.attn_weights
             return eager_loss
         recording, loss = hit
         self._fresh_shadow()
         recording.replay()
+        if key in self._attn:                       # a replay runs no Python forward: publish THIS shape's views of the maps it wrote
+            self.model.cap_decoder.attn_weights = self._attn[key]
         self.model._ps.shadow_replayed()            # the replayed optimizer rewrote the shadow
         return loss
 
