@@ -409,6 +409,36 @@ int vct_enc_frontend_ex_fwd(const vct_enc_frontend_ex_desc* d, void* stream);
 int vct_enc_frontend_ex_bwd(const vct_enc_frontend_ex_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Row routing between the layers of the hierarchical multi-modal encoder (csrc/vct_hmm_mix.hip).  Stream j of the reference's
+ * HMMEncoder passes through the LAST n_j of the L = max_j n_j shared layers: layer i takes, on the rows of stream j, the previous
+ * layer's output when L - n_j < i and the stack input mm_src otherwise (MMEncoder.py:385-398).  The host turns that into one table
+ * per layer, take uint8 [S]: 1 = the row continues from the previous layer's output, 0 = it restarts from the stack input.
+ *   fwd:  x[b, s, :] = take[s] ? y[b, s, :] : x0[b, s, :]          bitwise copy, out of place, one launch
+ *   bwd, from the gradient dx of a layer's input, one launch:
+ *         dy[b, s, :]  = take[s] ? dx[b, s, :] : 0                  the gradient handed to the previous layer's output (exact zeros)
+ *         acc[b, s, :]                                              fp32 [B*S, d], the stack input's gradient summed over the layers:
+ *                        init != 0: WRITTEN, float(dx) on the restarting rows and 0 on the others (no memset precedes it);
+ *                        init == 0: += float(dx) on the restarting rows, the others are not touched
+ *         with dx0 != NULL (layer 0, where every row restarts): dx0 = round_to_dtype(acc + float(dx)); dy and acc are not written,
+ *         take is not read (all may be NULL but acc); init must be 0.
+ *   The sum runs per element in the order of the launches (top layer first); no atomics, bitwise reproducible run to run.
+ * y / x0 / x / dx / dy / dx0: dtype rows of d (16-byte aligned, d a multiple of 8 bf16 / 4 fp32, VCT_E_ALIGN otherwise like the
+ * front-end kernels); 1 <= S <= 1024.  Null pointers / bad enums: VCT_E_ARG, S or B out of range: VCT_E_SHAPE, before any device use.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct vct_hmm_mix_desc {
+  int32_t dtype, B, S, d;
+  int32_t init, reserved;                   /* bwd: init != 0 writes acc instead of adding to it */
+  const uint8_t* take;                      /* [S] */
+  const void* y; const void* x0; void* x;   /* fwd: previous output, stack input -> layer input, each [B*S, d] */
+  const void* dx;                           /* bwd: [B*S, d] */
+  void* dy;                                 /* bwd: [B*S, d] (not with dx0) */
+  float* acc;                               /* bwd: fp32 [B*S, d] */
+  void* dx0;                                /* bwd, layer 0: [B*S, d] or NULL */
+} vct_hmm_mix_desc;
+int vct_hmm_mix_fwd(const vct_hmm_mix_desc* d, void* stream);
+int vct_hmm_mix_bwd(const vct_hmm_mix_desc* d, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Token embedding: x[n] = dropout(table[ids[n]] + pos[n % S])   (no sqrt(d) scaling)
  * replaces: nn.Embedding(padding_idx) + PositionalEmbedding (CapDecoder.py:26,48; Embedding.py:23-25).
  * ids: int64 [N] read with element stride id_stride from ids + b*id_batch_stride (so the token-shift

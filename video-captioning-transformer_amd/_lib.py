@@ -142,6 +142,12 @@ class EncFrontendExDesc(C.Structure):
                 ("d_modal", vp), ("d_emb", vp), ("dpre", vp), ("param_ws", vp)]
 
 
+class HmmMixDesc(C.Structure):
+    """include/vct_hip.h, vct_hmm_mix_desc: row routing between the layers of the hierarchical encoder."""
+    _fields_ = [("dtype", i32), ("B", i32), ("S", i32), ("d", i32), ("init", i32), ("reserved", i32),
+                ("take", vp), ("y", vp), ("x0", vp), ("x", vp), ("dx", vp), ("dy", vp), ("acc", vp), ("dx0", vp)]
+
+
 DEC_PRO = {"none": 0, "embed": 1, "ln": 2, "ln_ln": 3, "self_attn": 4, "cross_attn": 5}
 
 _SIGS = {
@@ -172,6 +178,8 @@ _SIGS = {
     "vct_mm_frontend_bwd": (C.c_int, [C.POINTER(MmFrontendDesc), vp]),
     "vct_enc_frontend_ex_fwd": (C.c_int, [C.POINTER(EncFrontendExDesc), vp]),
     "vct_enc_frontend_ex_bwd": (C.c_int, [C.POINTER(EncFrontendExDesc), vp]),
+    "vct_hmm_mix_fwd": (C.c_int, [C.POINTER(HmmMixDesc), vp]),
+    "vct_hmm_mix_bwd": (C.c_int, [C.POINTER(HmmMixDesc), vp]),
     "vct_embed_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, vp, vp, vp, u32, f32, vp]),
     "vct_embed_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, i64, vp, vp, vp, i64, C.c_int, vp, u32, f32, vp]),
     "vct_sce_loss": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, i64, f32, vp, vp, i64, vp, vp]),

@@ -318,3 +318,93 @@ class EncoderEngine(_StackBase):
         if bucket_ready is not None:
             bucket_ready("enc_layer", 0)
 
+
+class HMMEncoderEngine(EncoderEngine):
+    """HMMEncoder: model/MMEncoder.py:313-402 of the reference.  MultiModalEncoder's front end (every option, one stream or several),
+    then cfg['layers'] = max(cfg['hmm_layers']) shared layers `trans_enc_layers.{l}.*` with NO stack-final norm.  Stream j goes
+    through the last hmm_layers[j] of them: with target[j] = L - hmm_layers[j], layer i reads the previous layer's output on the
+    rows of stream j when target[j] < i and the stack input mm_src otherwise -- in the layers before that its rows are still keys
+    and values of the other streams, and their outputs are dropped.  The unfused per-layer schedule with ops.hmm_mix_fwd between
+    the layers 1 .. max(target); the backward routes each layer's input gradient back (ops.hmm_mix_bwd) and sums the stack
+    input's share over the layers max(target) .. 0 in an fp32 accumulator.  Equal depths launch no mix in either direction."""
+
+    def __init__(self, ps, prefix, cfg, seed, pe_buffer: torch.Tensor):
+        super().__init__(ps, prefix, cfg, seed, pe_buffer)
+        self.lps = [f"trans_enc_layers.{l}." for l in range(cfg["layers"])]
+        self._take = {}
+
+    def _ss_ok(self, Lr: int, Lm: int, Bn: int) -> bool:
+        """No sample-stationary form of this stack (nor of its backward, nor the one-stream front end folded into that launch)."""
+        return False
+
+    @staticmethod
+    def take_table(layers, Ts):
+        """uint8 [L, S], L = max(layers), S = sum(T_i + 1): take[i, s] = 1 where layer i reads the previous layer's output on row s
+        (target[j] = L - layers[j] < i for the stream j that owns s), 0 where it restarts from the stack input."""
+        import numpy as np
+        if len(layers) != len(Ts):
+            raise ValueError(f"hierarchical encoder: {len(layers)} layer counts for {len(Ts)} feature streams")
+        L = max(layers)
+        target = np.concatenate([np.full(t + 1, L - n, np.int64) for n, t in zip(layers, Ts)])
+        return (target[None, :] < np.arange(L)[:, None]).astype(np.uint8)
+
+    def take_rows(self, Ts):
+        """(take uint8 [L, S] on the device, max(target)) for the frame counts Ts, built once per frame-count tuple."""
+        r = self._take.get(Ts)
+        if r is None:
+            layers = self.cfg["hmm_layers"]
+            r = self._take[Ts] = (torch.from_numpy(self.take_table(layers, Ts)).to(self.dev), max(layers) - min(layers))
+        return r
+
+    def _stack_fwd(self, b, x, B, Te, kpm) -> torch.Tensor:
+        """The layers on the stack input x [B*Te, d]; returns the memory: the last layer's norm2 output."""
+        take, top = self.take_rows(self.mm_Ts if self.mm_Ts is not None else (Te - 1,))
+        x0 = x
+        for l in range(self.cfg["layers"]):
+            lp, tag, site = self.lps[l], self.tags[l], self.sites[l]
+            if 1 <= l <= top:
+                x = ops.hmm_mix_fwd(x, x0, take[l], b.get(tag + "xin", tuple(x0.shape), self.dt), B, Te)
+            b.t[tag + "x"] = x
+            x1 = self._attn_ln_fwd(b, tag + "sa.", tag + "n1.", lp + "self_attn.", lp + "norm1.", x, x, B, Te, Te, False, kpm,
+                                   site + 1, site + 2)
+            f = self._ffn_fwd(b, tag + "ff.", lp, x1, site + 3)
+            x = self._ln_fwd(b, tag + "n2.", lp + "norm2.", f, x1, site + 4)
+        b.t["x_last"] = x
+        return x
+
+    def backward(self, dmem: torch.Tensor, bucket_ready=None, join: bool = True):
+        """As EncoderEngine.backward's unfused schedule (side stream, bucket callbacks, join), without a final norm and with the
+        row routing's backward behind each layer's dX chain."""
+        b = self.cur
+        B, T = self.shape
+        Te, L = T + 1, self.cfg["layers"]
+        kpm = b.t["kpm_used"]
+        take, top = self.take_rows(self.mm_Ts if self.mm_Ts is not None else (T,))
+        acc = b.get("hmm.acc", (B * Te, self.cfg["d"]), torch.float32) if top > 0 else None
+        dx = dmem
+        for l in reversed(range(L)):
+            lp, tag, site = self.lps[l], self.tags[l], self.sites[l]
+            x, x1 = b.t[tag + "x"], b.t[tag + "n1.y"]
+            ds2, df = self._ln_bwd(b, tag + "n2.", lp + "norm2.", dx, b.t[tag + "ff.f"], x1, site + 4)
+            dx1 = self._ffn_bwd(b, tag + "ff.", lp, df, x1, site + 3, ds2)
+            ds1, da = self._ln_bwd(b, tag + "n1.", lp + "norm1.", dx1, b.t[tag + "sa.a"], x, site + 2)
+            dx = self._attn_block_bwd(b, tag + "sa.", lp + "self_attn.", da, x, x, B, Te, Te, False, kpm, site + 1, True, ds1)
+            if 1 <= l <= top:       # the previous layer's output gets the continuing rows, the accumulator the restarting ones
+                dx = ops.hmm_mix_bwd(dx, take[l], acc, B, Te, dy=b.get(tag + "dy", tuple(dx.shape), self.dt), init=(l == top))
+            elif l == 0 and top > 0:
+                dx = ops.hmm_mix_bwd(dx, None, acc, B, Te, dx0=b.get("hmm.dx0", tuple(dx.shape), self.dt))
+            if l > 0:
+                if bucket_ready is None and self.enc_dw_main and self.main_stream is not None:
+                    self.flush_dw_across(self.main_stream)
+                else:
+                    self.flush_dw()
+            if bucket_ready is not None and l > 0:
+                self.flush_ln_grads(b)
+                self.bucket_on_side(bucket_ready, "enc_layer", l)
+        self._frontend_bwd(dx)
+        self.flush_ln_grads(b)
+        if bucket_ready is None and self.enc_dw_main >= 2 and self.main_stream is not None:
+            self.flush_dw_across(self.main_stream)
+        self.join_side()
+        if bucket_ready is not None:
+            bucket_ready("enc_layer", 0)

@@ -16,7 +16,7 @@ from ..engine import ParamSet, first_input, memory_len
 from .CapDecoder import CapDecoder, grad_ready_order_decoder
 from .CapPreprocessor import CapPreprocessor
 from .Matching import Matching, TextEncoder
-from .MMEncoder import MultiModalEncoder, grad_ready_order_encoder
+from .MMEncoder import HMMEncoder, MultiModalEncoder
 
 _DTYPES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp32": torch.float32, "float32": torch.float32}
 
@@ -63,10 +63,12 @@ class MMT4Caption(nn.Module):
             vocab_size=self.cap_preprocessor.tokenizer.vocab_size, pad_id=self.cap_preprocessor.pad_id,
             sce_loss_alpha=dec_cfg["sce_loss_alpha"], custom_decoder_type=dec_cfg.get("layer_type", None),
             activation=model_config["activation"], device=device, compute_dtype=self.compute_dtype)
-        if enc_cfg.get("type", "mme") != "mme":
-            raise NotImplementedError("video_encoder.type 'simple'/'hmme' are outside the accelerated caption path")
+        enc_type = enc_cfg.get("type", "mme")
+        if enc_type not in ("mme", "hmme"):
+            raise NotImplementedError(f"video_encoder.type {enc_type!r} is outside the accelerated caption path ('mme' and 'hmme' are on it)")
         mme = enc_cfg["mme"]
-        self.video_encoder = MultiModalEncoder(
+        # 'hmme': video_encoder.layer is the per-stream list of depths, the options come from the `mme` block (MMT4Caption.py of the reference)
+        self.video_encoder = (HMMEncoder if enc_type == "hmme" else MultiModalEncoder)(
             d_feats=model_config["modal_shape"], d_model=model_config["embed_dim"], nhead=enc_cfg["nhead"],
             dim_feedforward=enc_cfg["feedforward"], num_encoder_layers=enc_cfg["layer"], dropout=model_config["dropout"],
             activation=model_config["activation"], global_type=mme["aggregation"],
@@ -87,8 +89,8 @@ class MMT4Caption(nn.Module):
     def _build_flat(self):
         named = dict(self.named_parameters())
         order = (grad_ready_order_decoder("cap_decoder.", self.cap_decoder.cfg["layers"]) +
-                 grad_ready_order_encoder("video_encoder.", self.video_encoder.cfg["layers"], self.video_encoder.num_modal,
-                                          self.video_encoder.cfg["temporal_type"], self.video_encoder.do_norm))
+                 self.video_encoder._order("video_encoder.", self.video_encoder.cfg["layers"], self.video_encoder.num_modal,
+                                           self.video_encoder.cfg["temporal_type"], self.video_encoder.do_norm))
         order += [n for n in named if n not in set(order)]   # matching.* (not on the caption path)
         dev = named[order[0]].device
         self._ps = ParamSet([(n, named[n]) for n in order], dev, self.compute_dtype, no_shadow=("cap_decoder.tgt_to_emb.weight",))
@@ -129,13 +131,17 @@ class MMT4Caption(nn.Module):
     def grad_buckets(self):
         """Contiguous [start, end) element ranges of the flat gradient buffer in the order the backward
         pass completes them: generator | decoder norm + top layer | ... | decoder layer 0 | token embedding |
-        encoder norm + top layer | ... | encoder layer 0 + unify (+ parameters outside the caption path)."""
+        encoder norm + top layer | ... | encoder layer 0 + unify (+ parameters outside the caption path).  The hierarchical encoder
+        has no stack-final norm: its first bucket starts at the top layer's norm2."""
         ps, o = self._ps, self._ps.offsets
-        Ld, Le = self.cap_decoder.cfg["layers"], self.video_encoder.cfg["layers"]
+        enc = self.video_encoder
+        Ld, Le = self.cap_decoder.cfg["layers"], enc.cfg["layers"]
+        enc_layers = "video_encoder." + enc.layers_at
+        enc_first = "video_encoder." + enc.final_norm + "weight" if enc.final_norm else f"{enc_layers}{Le - 1}.norm2.weight"
         cuts = [0, o["cap_decoder.decoder.norm.weight"]]
         cuts += [o[f"cap_decoder.decoder.layers.{l}.norm3.weight"] for l in reversed(range(Ld - 1))]
-        cuts += [o["cap_decoder.tgt_to_emb.weight"], o["video_encoder.transformer_encoder.norm.weight"]]
-        cuts += [o[f"video_encoder.transformer_encoder.layers.{l}.norm2.weight"] for l in reversed(range(Le - 1))]
+        cuts += [o["cap_decoder.tgt_to_emb.weight"], o[enc_first]]
+        cuts += [o[f"{enc_layers}{l}.norm2.weight"] for l in reversed(range(Le - 1))]
         cuts.append(ps.total)
         return [(cuts[i], cuts[i + 1]) for i in range(len(cuts) - 1)]
 

@@ -481,6 +481,39 @@ def enc_frontend_ex_bwd(dx, dus, B, Ts, *, agg="avg", us=None, temp=None, emb_w=
     return dus
 
 
+def _hmm_desc(t, B, S, take):
+    if t.dim() != 2 or t.shape[0] != B * S:
+        raise ValueError(f"hierarchical encoder mix: rows [B*S, d] = [{B * S}, d] expected, got {tuple(t.shape)}")
+    if take is not None and (take.dtype != torch.uint8 or take.numel() != S or not take.is_contiguous()):
+        raise ValueError("hierarchical encoder mix: take must be contiguous uint8 [S]")
+    desc = L.HmmMixDesc()
+    desc.dtype, desc.B, desc.S, desc.d, desc.take = L.dtype_code(t.dtype), B, S, t.shape[1], L.ptr(take)
+    return desc
+
+
+def hmm_mix_fwd(y, x0, take, x, B, S):
+    """Input of a layer of the hierarchical encoder (include/vct_hip.h, vct_hmm_mix_fwd): x[b, s] = y[b, s] (the previous layer's
+    output) where take[s], else x0[b, s] (the stack input); y / x0 / x [B*S, d], take uint8 [S]."""
+    desc = _hmm_desc(x, B, S, take)
+    desc.y, desc.x0, desc.x = y.data_ptr(), x0.data_ptr(), x.data_ptr()
+    L.check(L.load().vct_hmm_mix_fwd(L.C.byref(desc), L.stream_ptr()), "vct_hmm_mix_fwd")
+    return x
+
+
+def hmm_mix_bwd(dx, take, acc, B, S, *, dy=None, dx0=None, init: bool = False):
+    """Backward of hmm_mix_fwd from the gradient dx [B*S, d] of a layer's input, acc fp32 [B*S, d]: dy <- dx on the continuing rows
+    and 0 on the others, acc <- the restarting rows (init: written, 0 elsewhere; else added to).  At layer 0 (take = None):
+    dx0 <- acc + dx, nothing else is written.  Returns dy (or dx0)."""
+    if acc.dtype != torch.float32 or tuple(acc.shape) != tuple(dx.shape):
+        raise ValueError("hierarchical encoder mix: acc must be fp32 with the shape of dx")
+    if (dy is None) == (dx0 is None):
+        raise ValueError("hierarchical encoder mix: exactly one of dy (layers above 0) and dx0 (layer 0)")
+    desc = _hmm_desc(dx, B, S, take if dx0 is None else None)
+    desc.dx, desc.dy, desc.acc, desc.dx0, desc.init = dx.data_ptr(), L.ptr(dy), acc.data_ptr(), L.ptr(dx0), int(bool(init))
+    L.check(L.load().vct_hmm_mix_bwd(L.C.byref(desc), L.stream_ptr()), "vct_hmm_mix_bwd")
+    return dy if dx0 is None else dx0
+
+
 def embed_fwd(ids, S, table, pos, x, dropout: Drop = None):
     """ids: int64 [B, S_total] (row stride = ids.stride(0)); uses the first S columns of each row."""
     B = ids.shape[0]

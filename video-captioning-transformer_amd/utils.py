@@ -22,8 +22,8 @@ class Config:
             self.data = json.load(f)
 
     def check(self):
-        if self.data["model"]["video_encoder"].get("type", "mme") != "mme":
-            raise ValueError("only the 'mme' video encoder is on the accelerated caption path")
+        if self.data["model"]["video_encoder"].get("type", "mme") not in ("mme", "hmme"):
+            raise ValueError("only the 'mme' and 'hmme' video encoders are on the accelerated caption path")
 
 
 def setup_seed(seed: int):
