@@ -472,6 +472,60 @@ int vct_sce_loss(int dtype, int N, int S, int V, const void* logits, int64_t ldl
                  int64_t ld_dl, float* row_ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The video-text matching head (csrc/vct_match.hip), fp32 end to end.
+ * replaces: ClipSymmetricalLoss / ClipSymmetricalLoss_WithDualSoftmax (loss.py:7-67) as called by Matching.forward
+ * (Matching.py:27-30: loss_fn(text_feat, vid_feat)) and their autograd backward.
+ *   sim[i, j] = t^_i . v^_j, both sides L2-normalised per row (text rows i, video columns j; no epsilon, as the reference)
+ *   CSL:      logits = sim * exp(*temp) (VCT_MATCH_TEMP_EXP) or sim (VCT_MATCH_TEMP_NONE)
+ *   CSL_WDS:  logits = sim * softmax(sim / *temp, over i) * B     (VCT_MATCH_TEMP_DIV only)
+ *   loss = (CE(logits, arange) + CE(logits^T, arange)) / 2, mean reduction.
+ * text / vid [B, Dt] with leading dimensions (multiples of 4, 16-byte aligned bases); temp: DEVICE scalar, NULL exactly when
+ * temp_kind is VCT_MATCH_TEMP_NONE.  loss [1].  dvid [B, Dt] or NULL (= forward only): the gradient w.r.t. the UN-normalised vid.
+ * dtemp [1] or NULL: written only when temp and dvid are given.  sim [B, ld_sim] or NULL: the logits as the loss saw them.
+ * 1 <= B <= 256, Dt a multiple of 4 up to 1024 (VCT_E_SHAPE otherwise); workspace: vct_match_loss_workspace_bytes(B, Dt) bytes
+ * (0 for an unsupported shape), 16-byte aligned, owned by the caller.  No allocation, no synchronisation, no host read; every
+ * reduction has a fixed order and there is no floating-point atomic: two calls on the same inputs agree bitwise, and a
+ * forward-only call returns the same loss bits.  Launches: CSL 4 (3 forward only), CSL_WDS 5 (4 forward only).
+ * --------------------------------------------------------------------------------------------- */
+enum { VCT_MATCH_CSL = 0, VCT_MATCH_CSL_WDS = 1 };
+enum { VCT_MATCH_TEMP_NONE = 0, VCT_MATCH_TEMP_EXP = 1, VCT_MATCH_TEMP_DIV = 2 };
+typedef struct vct_match_loss_desc {
+  int32_t B, Dt, loss_kind, temp_kind;
+  const float* text; int64_t ld_text;
+  const float* vid; int64_t ld_vid;
+  const float* temp;
+  float* loss;
+  float* dvid; int64_t ld_dvid;
+  float* dtemp;
+  float* sim; int64_t ld_sim;
+  void* workspace; int64_t workspace_bytes;
+} vct_match_loss_desc;
+int vct_match_loss(const vct_match_loss_desc* d, void* stream);
+int64_t vct_match_loss_workspace_bytes(int B, int Dt);
+
+/* The aggregation row of every sample <-> the matching head (MMEncoder.py: agg_feat = memory[:, 0]), and the mix of the two tasks'
+ * gradients of `memory` (MMT4Caption.py:146: loss_beta * cap_loss + (1 - loss_beta) * match_loss).
+ *   fwd: agg[b, :] = float(mem[b * Te, :])                                                     mem [B * Te, d] of dtype, agg fp32 [B, d]
+ *   bwd: dmem[b * Te + r, :] = beta * dmem[b * Te + r, :] + (r == 0 ? (1 - beta) * dagg[b, :] : 0)   over the whole [B * Te, d], in place
+ *        (fp32 products rounded separately, one add, one rounding to dtype); empty != 0: dmem holds nothing yet and is NOT read
+ *        (the match task: beta = 0, no zero fill needed).
+ * d a multiple of 8 (bf16) / 4 (fp32), 16-byte aligned bases (VCT_E_ALIGN); 0 <= beta <= 1 (VCT_E_ARG). */
+typedef struct vct_match_agg_desc {
+  int32_t dtype, B, Te, d;
+  int32_t empty; float beta;
+  const void* mem; float* agg;       /* fwd */
+  const float* dagg; void* dmem;     /* bwd */
+} vct_match_agg_desc;
+int vct_match_agg_fwd(const vct_match_agg_desc* d, void* stream);
+int vct_match_agg_bwd(const vct_match_agg_desc* d, void* stream);
+
+/* x[0 .. n) *= s (fp32, 16-byte aligned base): the caption task's share of the flat gradient buffer times loss_beta. */
+int vct_scale(float* x, int64_t n, float s, void* stream);
+/* out[0 .. n) = a * x + b * y (fp32; y NULL: a * x; out may alias x or y): loss = loss_beta * cap_loss + (1 - loss_beta) * match_loss
+ * on the device, and small scaled copies between the head's buffers and the flat gradient buffer. */
+int vct_axpby(float* out, const float* x, float a, const float* y, float b, int64_t n, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Batch assembly from a DEVICE-RESIDENT feature store (a split's clips packed into store [rows, E] fp32, clip i =
  * rows offsets[i] .. offsets[i+1]): out[b, t, :] = store[offsets[idx[b]] + t] for t < len(clip idx[b]), else 0;
  * mask[b, t] = 1 where padded.  out: [B, Tmax, E] of out_dtype (fp32, or bf16 = the encoder's compute type, which

@@ -148,6 +148,23 @@ class HmmMixDesc(C.Structure):
                 ("take", vp), ("y", vp), ("x0", vp), ("x", vp), ("dx", vp), ("dy", vp), ("acc", vp), ("dx0", vp)]
 
 
+MATCH_LOSS = {"CSL": 0, "CSL_WDS": 1}
+MATCH_TEMP = {"none": 0, "exp": 1, "div": 2}
+
+
+class MatchLossDesc(C.Structure):
+    """include/vct_hip.h, vct_match_loss_desc: the contrastive video-text loss, forward and backward."""
+    _fields_ = [("B", i32), ("Dt", i32), ("loss_kind", i32), ("temp_kind", i32), ("text", vp), ("ld_text", i64), ("vid", vp), ("ld_vid", i64),
+                ("temp", vp), ("loss", vp), ("dvid", vp), ("ld_dvid", i64), ("dtemp", vp), ("sim", vp), ("ld_sim", i64),
+                ("workspace", vp), ("workspace_bytes", i64)]
+
+
+class MatchAggDesc(C.Structure):
+    """include/vct_hip.h, vct_match_agg_desc: the aggregation row of every sample <-> the matching head."""
+    _fields_ = [("dtype", i32), ("B", i32), ("Te", i32), ("d", i32), ("empty", i32), ("beta", f32), ("mem", vp), ("agg", vp),
+                ("dagg", vp), ("dmem", vp)]
+
+
 DEC_PRO = {"none": 0, "embed": 1, "ln": 2, "ln_ln": 3, "self_attn": 4, "cross_attn": 5}
 
 _SIGS = {
@@ -180,6 +197,12 @@ _SIGS = {
     "vct_enc_frontend_ex_bwd": (C.c_int, [C.POINTER(EncFrontendExDesc), vp]),
     "vct_hmm_mix_fwd": (C.c_int, [C.POINTER(HmmMixDesc), vp]),
     "vct_hmm_mix_bwd": (C.c_int, [C.POINTER(HmmMixDesc), vp]),
+    "vct_match_loss": (C.c_int, [C.POINTER(MatchLossDesc), vp]),
+    "vct_match_loss_workspace_bytes": (i64, [C.c_int, C.c_int]),
+    "vct_match_agg_fwd": (C.c_int, [C.POINTER(MatchAggDesc), vp]),
+    "vct_match_agg_bwd": (C.c_int, [C.POINTER(MatchAggDesc), vp]),
+    "vct_scale": (C.c_int, [vp, i64, f32, vp]),
+    "vct_axpby": (C.c_int, [vp, vp, f32, vp, f32, i64, vp]),
     "vct_embed_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, vp, vp, vp, u32, f32, vp]),
     "vct_embed_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, i64, vp, vp, vp, i64, C.c_int, vp, u32, f32, vp]),
     "vct_sce_loss": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, i64, f32, vp, vp, i64, vp, vp]),

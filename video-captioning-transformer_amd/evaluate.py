@@ -71,19 +71,30 @@ def eval_epoch(model, dataloader, max_len: int = 30, beam_size: Optional[int] = 
 
 
 @torch.no_grad()
-def val_epoch(model, dataloader, mode: str = "caption") -> float:
-    """train.py:150-167 for the caption task: mean teacher-forced loss over the loader, model in eval mode."""
-    if mode != "caption":
-        raise NotImplementedError("only the caption task is on the accelerated path")
+def val_epoch(model, dataloader, mode: str = "caption", text_feats_fn=None):
+    """train.py:150-167: mean loss over the loader, model in eval mode -- teacher-forced for 'caption' (a float), the contrastive
+    loss for 'match' (a float), (loss, cap_loss, match_loss) for 'cross'.  text_feats_fn(captions, vids) -> fp32
+    [B, text_encoder.dim] (match / cross); without it model.text_encoder(captions).  One device->host sync per epoch."""
+    if mode not in ("caption", "match", "cross"):
+        raise ValueError(f"unknown task {mode!r}")
     model.eval()
     model.mode(mode)
+    model.check_task(mode)
     dev = model.device
-    total, n = torch.zeros(1, device=dev), 0
-    for v_feats, v_masks, captions, _vids in dataloader:
+    total, n = torch.zeros(3 if mode == "cross" else 1, device=dev), 0
+    for v_feats, v_masks, captions, vids in dataloader:
         v_feats = [f.to(dev, non_blocking=True) for f in v_feats]
         v_masks = [m.to(dev, non_blocking=True) for m in v_masks]
-        total += model(v_feats, v_masks, captions).detach().reshape(1)
+        if mode == "caption":
+            total += model(v_feats, v_masks, captions).detach().reshape(1)
+        else:
+            text = text_feats_fn(captions, vids) if text_feats_fn is not None else model.text_encoder(captions)
+            text = text.to(dev, non_blocking=True) if torch.is_tensor(text) else text
+            out = model(v_feats, v_masks, captions, text_feats=text)
+            total += torch.stack([o.detach() for o in out]) if mode == "cross" else out.detach().reshape(1)
         n += 1
+    if mode == "cross":
+        return tuple(v / max(n, 1) for v in total.tolist())
     return float(total) / max(n, 1)
 
 

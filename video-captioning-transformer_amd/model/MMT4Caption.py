@@ -1,7 +1,8 @@
-"""MMT4Caption -- drop-in for the reference's model/MMT4Caption.py:15-211 on the caption task.
+"""MMT4Caption -- drop-in for the reference's model/MMT4Caption.py:15-211: the caption task on every executor, the video-text
+matching task ('match') and both together ('cross') on the eager one.
 
 Same constructor (`MMT4Caption(cfg['model'], device)`), `forward(video_feats, video_masks, captions)`,
-`caption_forward`, `greedy_decode`, `mode`, attributes (`cap_preprocessor`, `cap_decoder`,
+`caption_forward`, `match_forward`, `cross_forward`, `greedy_decode`, `mode`, attributes (`cap_preprocessor`, `cap_decoder`,
 `video_encoder`, `matching`, `device`, `f_type`) and state_dict keys.  All parameters live in ONE
 flat fp32 buffer laid out in gradient-ready order (with a matching flat gradient buffer and a bf16
 shadow), so the data-parallel gradient exchange and the optimizer work on contiguous slices."""
@@ -15,7 +16,7 @@ from .. import ops
 from ..engine import ParamSet, first_input, memory_len
 from .CapDecoder import CapDecoder, grad_ready_order_decoder
 from .CapPreprocessor import CapPreprocessor
-from .Matching import Matching, TextEncoder
+from .Matching import Matching, TextEncoder, check_text_feats
 from .MMEncoder import HMMEncoder, MultiModalEncoder
 
 _DTYPES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp32": torch.float32, "float32": torch.float32}
@@ -40,6 +41,49 @@ class _CaptionFn(torch.autograd.Function):
         return (None, None, None, None) + (None,) * len(m._ps.names)
 
 
+class _MatchFn(torch.autograd.Function):
+    """loss = match_forward(...) as ONE autograd node: encoder + matching head forward, the reverse schedule in backward.  The
+    decoder is never entered and its parameters get no gradient (.grad stays None, as in the reference)."""
+
+    @staticmethod
+    def forward(ctx, model, feats, mask, text, *params):
+        ctx.model = model
+        ctx.st = model._match_forward_kernels(feats, mask, text, model.training, backward=True)
+        return ctx.st["loss"][0].clone()
+
+    @staticmethod
+    def backward(ctx, gloss):
+        m = ctx.model
+        m._match_backward_kernels(ctx.st)
+        a = m.encoder_param_begin
+        m._ps.install_grads()
+        if not m._unit_loss_grad:
+            m._ps.gflat[a:].mul_(gloss)
+        return (None, None, None, None) + (None,) * len(m._ps.names)
+
+
+class _CrossFn(torch.autograd.Function):
+    """(loss, cap_loss, match_loss) = cross_forward(...) as ONE autograd node; only `loss` is differentiable (train.py:133-136
+    backpropagates nothing else)."""
+
+    @staticmethod
+    def forward(ctx, model, feats, mask, ids, text, *params):
+        ctx.model = model
+        loss, cap, match, ctx.st = model._cross_forward_kernels(feats, mask, ids, text, model.training, backward=True)
+        out = (loss.clone().reshape(()), cap.clone().reshape(()), match.clone().reshape(()))
+        ctx.mark_non_differentiable(out[1], out[2])
+        return out
+
+    @staticmethod
+    def backward(ctx, gloss, _gcap, _gmatch):
+        m = ctx.model
+        m._cross_backward_kernels(ctx.st)
+        m._ps.install_grads()
+        if not m._unit_loss_grad:
+            m._ps.gflat.mul_(gloss)
+        return (None, None, None, None, None) + (None,) * len(m._ps.names)
+
+
 class MMT4Caption(nn.Module):
     overlap_enc_bwd = True      # encoder backward beside the decoder's tail (A/B switch)
     overlap_dec_prefix = True   # decoder embedding + bottom self-attention beside the encoder forward (A/B switch)
@@ -55,7 +99,7 @@ class MMT4Caption(nn.Module):
 
         self.cap_preprocessor = CapPreprocessor(model_config["tokenizer"], device=device,
                                                 vocab_size=model_config.get("vocab_size"))
-        self.text_encoder = TextEncoder(model_config["text_enc_type"], device=device)
+        self.text_encoder = TextEncoder(model_config["text_enc_type"], device=device, dim=model_config.get("text_enc_dim"))
         dec_cfg, enc_cfg = model_config["caption_decoder"], model_config["video_encoder"]
         self.cap_decoder = CapDecoder(
             num_layers=dec_cfg["layer"], embed_dim=model_config["embed_dim"], nhead=dec_cfg["nhead"],
@@ -79,10 +123,12 @@ class MMT4Caption(nn.Module):
                                      enable_tem=model_config["matching"]["enable_tem"],
                                      loss=model_config["matching"]["matching_loss"],
                                      loss_tem=model_config["matching"].get("temperature", None), device=device)
+        self._enc_type = enc_type
         self._ps: Optional[ParamSet] = None
         self._unit_loss_grad = False
         self._seed = None
         self._pending_enc_bwd = None      # train_step_kernels(defer_join=True): the encoder backward, not enqueued yet
+        self._mem = None                  # the encoder memory of the last caption forward
         self._build_flat()
 
     # ---- flat parameter storage --------------------------------------------------------------------
@@ -171,7 +217,7 @@ class MMT4Caption(nn.Module):
         if self.overlap_dec_prefix and dec.dev.type == "cuda" and dec.overlap_dw:
             # token embedding + the decoder's bottom self-attention block do not need the encoder: side stream, beside it
             dec.forward_prefix(B, Te, ids, training)
-        mem = enc.forward(feats, mask, training)
+        mem = self._mem = enc.forward(feats, mask, training)      # (kept for the matching head of the cross task)
         loss, logits = dec.forward(mem, B, Te, ids, training, want_logits=want_logits)
         self.cap_decoder._publish_attn(dec)
         return loss, logits
@@ -267,12 +313,128 @@ class MMT4Caption(nn.Module):
             raise ValueError(f"expected {n} feature streams (and as many masks, or None), got {len(video_feats)}")
         return list(video_feats), (list(video_masks) if video_masks is not None else None)
 
-    def forward(self, video_feats: List[torch.Tensor], video_masks: List[torch.Tensor], captions):
+    def forward(self, video_feats: List[torch.Tensor], video_masks: List[torch.Tensor], captions, text_feats=None):
+        """text_feats (match / cross): fp32 [B, text_encoder.dim] on the model's device; None = self.text_encoder(captions)."""
         if self.f_type == "caption":
             return self.caption_forward(video_feats, video_masks, captions)
-        if self.f_type in ("match", "cross"):
-            raise NotImplementedError("the video-text matching task is outside the MI355X caption path")
+        if self.f_type == "match":
+            return self.match_forward(video_feats, video_masks, captions, text_feats)
+        if self.f_type == "cross":
+            return self.cross_forward(video_feats, video_masks, captions, text_feats)
         raise ValueError
+
+    # ---- the matching task ('match') and both tasks ('cross'): eager executor, 'mme' encoder ------------------------------------
+    def check_task(self, task: Optional[str] = None):
+        """Refuse, before any device work, what the matching task is not built for."""
+        task = self.f_type if task is None else task
+        if task not in ("match", "cross"):
+            return
+        if getattr(self, "matching", None) is None:
+            raise ValueError(f"task {task!r} needs the matching head: model_config['matching'] is None")
+        if self._enc_type == "hmme":
+            raise NotImplementedError(f"task {task!r} with video_encoder.type 'hmme' is not built: the hierarchical encoder's agg_feats is "
+                                      "one scalar per sample ([B]), which the matching head's v_proj cannot take")
+
+    def _text_feats(self, captions, text_feats, B):
+        if text_feats is None:
+            text_feats = self.text_encoder(captions)
+        return check_text_feats(text_feats, B, self.text_encoder.dim, self.flat_params.device)
+
+    def _match_forward_kernels(self, feats, mask, text, training, backward, mem=None):
+        """Encoder forward (unless `mem` is given: the cross task's caption forward made it), the aggregation rows, the head."""
+        if mem is None:
+            if not self._ps.intact():
+                self._build_flat()
+            self._ps.refresh_shadow()
+            mem = self.video_encoder._engine().forward(feats, mask, training)
+        B, Te = first_input(feats).shape[0], memory_len(feats)
+        agg = self.matching._buf("agg", (B, mem.shape[1]), mem.device)
+        ops.match_agg_fwd(mem, agg, B, Te)
+        st = self.matching.head_forward(text, agg, backward=backward)
+        st["B"], st["Te"], st["mem"] = B, Te, mem
+        return st
+
+    def _head_backward_kernels(self, st):
+        """d(match loss) into the matching.* slice of the flat gradient buffer; returns d(match loss)/d(agg) fp32 [B, d]."""
+        mt, g = self.matching, self._ps.g
+        dagg = mt._buf("dagg", tuple(st["agg"].shape), st["agg"].device)
+        if mt.v_proj is not None:
+            dagg = mt.head_backward(st, dagg, g["matching.v_proj.weight"], g["matching.v_proj.bias"])
+        else:
+            dagg = mt.head_backward(st, dagg)
+        if mt.loss_fn.learned:
+            ops.axpby(g["matching.loss_fn.temperature"], st["dtemp"], 1.0)
+        return dagg
+
+    def _match_backward_kernels(self, st, hook=None):
+        enc = self.video_encoder._engine()
+        dagg = self._head_backward_kernels(st)
+        dmem = enc.cur.get("match.dmem", tuple(st["mem"].shape), st["mem"].dtype)
+        ops.match_agg_bwd(dmem, dagg, st["B"], st["Te"], 0.0, empty=True)     # every row written: no zero fill, the buffer is not read
+        enc.backward(dmem, hook)
+
+    def _cross_forward_kernels(self, feats, mask, ids, text, training, backward):
+        cap_loss, _ = self._forward_loss(feats, mask, ids, training)
+        st = self._match_forward_kernels(feats, mask, text, training, backward, mem=self._mem)
+        beta = float(self.loss_beta)
+        loss = ops.axpby(self.matching._buf("cross_loss", (1,), cap_loss.device), cap_loss.reshape(1), beta, st["loss"], 1.0 - beta)
+        return loss, cap_loss, st["loss"], st
+
+    def _cross_backward_kernels(self, st, hook=None):
+        dec, enc = self.cap_decoder._engine(), self.video_encoder._engine()
+        beta = float(self.loss_beta)
+        dmem = dec.backward(hook)                                  # the non-overlapped branch: ends with the side stream joined
+        ops.scale(self._ps.gflat[:self.encoder_param_begin], beta)   # the caption task's decoder-side gradients, times beta
+        dagg = self._head_backward_kernels(st)
+        a = self.caption_param_end
+        if a < self._ps.total:
+            ops.scale(self._ps.gflat[a:], 1.0 - beta)              # matching.*: only the match loss reaches them
+        ops.match_agg_bwd(dmem, dagg, st["B"], st["Te"], beta)     # beta * d(cap)/d(memory) + (1 - beta) * d(match)/d(memory), in place
+        enc.backward(dmem, hook)
+
+    def train_step_kernels_match(self, feats, mask, text_feats: torch.Tensor) -> torch.Tensor:
+        """The match task's step as one static kernel schedule, no autograd tape: encoder forward, aggregation rows, head, head
+        backward, d(memory) (only the aggregation rows are non-zero), encoder backward.  Gradients of the encoder and of matching.*
+        are WRITTEN into the flat gradient buffer; the decoder engine is never entered and its slice is not written.  Returns the
+        loss tensor [1]."""
+        self.check_task("match")
+        text = check_text_feats(text_feats, first_input(feats).shape[0], self.text_encoder.dim, self.flat_params.device)
+        st = self._match_forward_kernels(feats, mask, text, self.training, backward=True)
+        self._match_backward_kernels(st)
+        self._ps.weight_grads_valid = True
+        return st["loss"]
+
+    def train_step_kernels_cross(self, feats, mask, ids: torch.Tensor, text_feats: torch.Tensor):
+        """Both tasks in one step: the caption forward, the head on the same memory, the decoder backward, its gradients times
+        loss_beta, the head backward, beta * d(cap)/d(memory) + (1 - beta) * d(match)/d(memory), the encoder backward.  Same contract
+        as train_step_kernels.  Returns (loss, cap_loss, match_loss), three device tensors [1]."""
+        self.check_task("cross")
+        text = check_text_feats(text_feats, first_input(feats).shape[0], self.text_encoder.dim, self.flat_params.device)
+        loss, cap, match, st = self._cross_forward_kernels(feats, mask, ids, text, self.training, backward=True)
+        self._cross_backward_kernels(st)
+        self._ps.weight_grads_valid = True
+        return loss, cap, match
+
+    def match_forward(self, video_feats, video_masks, captions, text_feats=None):
+        """MMT4Caption.py:126-133 of the reference: the contrastive loss between the text features and the encoder's agg_feat."""
+        self.check_task("match")
+        feats, mask = self._video_inputs(video_feats, video_masks)
+        text = self._text_feats(captions, text_feats, first_input(feats).shape[0])
+        if not torch.is_grad_enabled():
+            return self._match_forward_kernels(feats, mask, text, self.training, backward=False)["loss"][0].clone()
+        return _MatchFn.apply(self, feats, mask, text, *[self._ps.params[n] for n in self._ps.names]).reshape(())
+
+    def cross_forward(self, video_feats, video_masks, captions, text_feats=None):
+        """MMT4Caption.py:135-147 of the reference: (loss_beta * cap_loss + (1 - loss_beta) * match_loss, cap_loss, match_loss);
+        the two task losses come back detached."""
+        self.check_task("cross")
+        text_ts, _text_mask_ts = self.cap_preprocessor(captions)
+        feats, mask = self._video_inputs(video_feats, video_masks)
+        text = self._text_feats(captions, text_feats, first_input(feats).shape[0])
+        if not torch.is_grad_enabled():
+            loss, cap, match, _ = self._cross_forward_kernels(feats, mask, text_ts, text, self.training, backward=False)
+            return loss[0].clone(), cap[0].clone(), match[0].clone()
+        return _CrossFn.apply(self, feats, mask, text_ts, text, *[self._ps.params[n] for n in self._ps.names])
 
     def caption_forward(self, video_feats, video_masks, captions):
         text_ts, _text_mask_ts = self.cap_preprocessor(captions)

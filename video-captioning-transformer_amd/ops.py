@@ -573,6 +573,90 @@ def sce_loss(logits, V, labels, S, pad_id, alpha, loss_out, dlogits, row_ws):
     return loss_out
 
 
+def match_loss_workspace_bytes(B: int, Dt: int) -> int:
+    """Bytes of caller-owned workspace ops.match_loss needs (include/vct_hip.h); raises for a shape the kernels do not take."""
+    n = int(L.load().vct_match_loss_workspace_bytes(int(B), int(Dt)))
+    if n <= 0:
+        raise ValueError(f"matching loss: batch {B} x text dimension {Dt} is outside the kernels' range "
+                         f"(1 <= batch <= 256, dimension a multiple of 4 up to 1024)")
+    return n
+
+
+def match_loss(text, vid, loss_out, workspace, *, kind: str = "CSL", temp=None, temp_kind: str = "none", dvid=None, dtemp=None, sim=None):
+    """The contrastive video-text loss, forward and backward in one call (include/vct_hip.h, vct_match_loss).  text / vid fp32
+    [B, Dt] row-major views; temp: fp32 device scalar for temp_kind 'exp' (CSL: sim * exp(temp)) / 'div' (CSL_WDS: sim / temp), None
+    for 'none'; loss_out fp32 [1]; dvid fp32 [B, Dt] or None (forward only); dtemp fp32 [1] or None; sim fp32 [B, B] or None (the
+    logits as the loss saw them); workspace: >= match_loss_workspace_bytes(B, Dt) bytes."""
+    B, Dt = text.shape
+    if tuple(vid.shape) != (B, Dt):
+        raise ValueError(f"matching loss: text {tuple(text.shape)} and video {tuple(vid.shape)} features must have one shape (square batches)")
+    for t in (text, vid, dvid, sim, loss_out, temp, dtemp):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError("matching loss: every operand is fp32")
+    need = match_loss_workspace_bytes(B, Dt)
+    d = L.MatchLossDesc()
+    d.B, d.Dt, d.loss_kind, d.temp_kind = B, Dt, L.MATCH_LOSS[kind], L.MATCH_TEMP[temp_kind]
+    d.text, d.ld_text, d.vid, d.ld_vid = text.data_ptr(), _ld(text), vid.data_ptr(), _ld(vid)
+    d.temp, d.loss, d.dtemp = L.ptr(temp), loss_out.data_ptr(), L.ptr(dtemp)
+    if dvid is not None:
+        d.dvid, d.ld_dvid = dvid.data_ptr(), _ld(dvid)
+    if sim is not None:
+        if tuple(sim.shape) != (B, B):
+            raise ValueError(f"matching loss: sim must be [{B}, {B}]")
+        d.sim, d.ld_sim = sim.data_ptr(), _ld(sim)
+    d.workspace, d.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    if d.workspace_bytes < need:
+        raise ValueError(f"matching loss: workspace of {d.workspace_bytes} bytes, {need} needed")
+    L.check(L.load().vct_match_loss(L.C.byref(d), L.stream_ptr()), "vct_match_loss")
+    return loss_out
+
+
+def _agg_desc(t, B, Te):
+    if t.dim() != 2 or t.shape[0] != B * Te or not t.is_contiguous():
+        raise ValueError(f"matching aggregation rows: contiguous [B*Te, d] = [{B * Te}, d] expected, got {tuple(t.shape)}")
+    d = L.MatchAggDesc()
+    d.dtype, d.B, d.Te, d.d = L.dtype_code(t.dtype), B, Te, t.shape[1]
+    return d
+
+
+def match_agg_fwd(mem, agg, B, Te):
+    """agg fp32 [B, d] <- memory row b * Te of every sample (the aggregation row of stream 0; include/vct_hip.h, vct_match_agg_fwd)."""
+    d = _agg_desc(mem, B, Te)
+    if agg.dtype != torch.float32 or tuple(agg.shape) != (B, mem.shape[1]) or not agg.is_contiguous():
+        raise ValueError("matching aggregation rows: agg must be contiguous fp32 [B, d]")
+    d.mem, d.agg = mem.data_ptr(), agg.data_ptr()
+    L.check(L.load().vct_match_agg_fwd(L.C.byref(d), L.stream_ptr()), "vct_match_agg_fwd")
+    return agg
+
+
+def match_agg_bwd(dmem, dagg, B, Te, beta: float, empty: bool = False):
+    """dmem[b*Te + r] <- beta * dmem[b*Te + r] + (r == 0 ? (1 - beta) * dagg[b] : 0), in place over the whole [B*Te, d]; empty: dmem
+    holds nothing yet and is not read (include/vct_hip.h, vct_match_agg_bwd)."""
+    d = _agg_desc(dmem, B, Te)
+    if dagg.dtype != torch.float32 or tuple(dagg.shape) != (B, dmem.shape[1]) or not dagg.is_contiguous():
+        raise ValueError("matching aggregation rows: dagg must be contiguous fp32 [B, d]")
+    d.dmem, d.dagg, d.beta, d.empty = dmem.data_ptr(), dagg.data_ptr(), float(beta), int(bool(empty))
+    L.check(L.load().vct_match_agg_bwd(L.C.byref(d), L.stream_ptr()), "vct_match_agg_bwd")
+    return dmem
+
+
+def scale(x: torch.Tensor, s: float):
+    """x *= s over a contiguous fp32 range (include/vct_hip.h, vct_scale)."""
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("scale: a contiguous fp32 tensor")
+    L.check(L.load().vct_scale(x.data_ptr(), x.numel(), float(s), L.stream_ptr()), "vct_scale")
+    return x
+
+
+def axpby(out: torch.Tensor, x: torch.Tensor, a: float, y: Optional[torch.Tensor] = None, b: float = 0.0):
+    """out = a * x + b * y over contiguous fp32 tensors of one size (y None: a * x; include/vct_hip.h, vct_axpby)."""
+    for t in (out, x, y):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != out.numel()):
+            raise ValueError("axpby: contiguous fp32 tensors of one size")
+    L.check(L.load().vct_axpby(out.data_ptr(), x.data_ptr(), float(a), L.ptr(y), float(b), out.numel(), L.stream_ptr()), "vct_axpby")
+    return out
+
+
 def warm(t: torch.Tensor):
     """Read-only pass over a tensor: pulls it into the memory-side cache for the launch that streams it next (include/vct_hip.h, vct_warm)."""
     L.check(L.load().vct_warm(t.data_ptr(), t.numel() * t.element_size(), L.stream_ptr()), "vct_warm")

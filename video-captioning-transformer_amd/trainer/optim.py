@@ -7,6 +7,19 @@ import torch
 from .. import ops
 
 
+def owned_range(model, task):
+    """[begin, end) of the flat parameter buffer the optimizer of `task` owns -- what the reference's filter(requires_grad) after
+    mode(task) keeps (train.py:24): 'caption' (or None) the decoder and the encoder, 'match' the encoder and matching.* (the decoder
+    is frozen), 'cross' everything."""
+    if task in (None, "caption"):
+        return 0, model.caption_param_end
+    if task == "match":
+        return model.encoder_param_begin, model._ps.total
+    if task == "cross":
+        return 0, model._ps.total
+    raise ValueError(f"unknown task {task!r}")
+
+
 class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam / AdamW semantics (reference train.py:24-31) as ONE kernel over the model's flat
     fp32 parameter buffer, which also rewrites the bf16 shadow the GEMMs read.  `param_groups[0]['lr']`
@@ -24,9 +37,10 @@ class FusedAdam(torch.optim.Optimizer):
         emb = "cap_decoder.tgt_to_emb.weight"
         a = ps.offsets[emb]
         self.skip = (a, a + (ps.params[emb].numel() + ps.ALIGN - 1) // ps.ALIGN * ps.ALIGN)
-        # the reference builds its optimizer over filter(requires_grad) (train.py:24): parameters outside the caption
-        # path (matching.*: frozen by mode('caption'), never given a gradient here) are neither stepped nor decayed
-        self.end = model.caption_param_end
+        # the reference builds its optimizer over filter(requires_grad) AFTER mode(task) (train.py:24): parameters outside the task's
+        # range (caption: matching.*, frozen and never given a gradient; match: the decoder) are neither stepped nor decayed
+        self.task = model.f_type
+        self.begin, self.end = owned_range(model, self.task)
         # lr / betas / eps / weight decay live in DEVICE memory (read by the kernel): a captured hipGraph or a recorded
         # launch list follows LR schedulers and load_state_dict instead of freezing the values of the recording step
         self.hyper = torch.zeros(8, dtype=torch.float32, device=ps.flat.device)
@@ -87,7 +101,7 @@ class FusedAdam(torch.optim.Optimizer):
         produce, and note that this step's step_range() calls must leave its flat range alone.  None: not steppable there."""
         ps = self.model._ps
         off = (dw.data_ptr() - ps.gflat.data_ptr()) // 4
-        if not self.dw_fusion or dw.dim() != 2 or dw.dtype != torch.float32 or not (0 <= off < self.end):
+        if not self.dw_fusion or dw.dim() != 2 or dw.dtype != torch.float32 or not (self.begin <= off < self.end):
             return None
         name, base = ps.name_at(off)
         shape = ps.params[name].shape
@@ -138,7 +152,7 @@ class FusedAdam(torch.optim.Optimizer):
     def step(self, closure=None):
         if not torch.cuda.is_current_stream_capturing():
             self.sync_hyper()
-        self.step_range(0, self.end)
+        self.step_range(self.begin, self.end)
         self.finish_ranges()
 
     # A/B switch: the optimizer's pass writes the stream-order packed weight copies itself (instead of vct_ss_pack launches behind it)
@@ -150,7 +164,7 @@ class FusedAdam(torch.optim.Optimizer):
     def step_range(self, a: int, b: int):
         """Adam on flat elements [a, b) only, without advancing the step counter (range-by-range stepping as
         gradient buckets complete); call finish_ranges() after the last range of the step."""
-        b = min(b, self.end)
+        a, b = max(a, self.begin), min(b, self.end)
         if b <= a:
             return
         lr, b1, b2, eps, wd = self._hyper_now()

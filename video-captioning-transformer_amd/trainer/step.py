@@ -1,4 +1,5 @@
-"""The step executor of the caption task (CaptionTrainer: eager, recorded launch list or captured hipGraph) and the epoch loop."""
+"""The step executor (CaptionTrainer: eager, recorded launch list or captured hipGraph; the match / cross tasks: eager only) and the
+epoch loop."""
 from typing import Optional
 import os
 
@@ -34,6 +35,10 @@ class CaptionTrainer:
         None: the VCT_FUSE_ADAM_KEEP_GRAD environment switch (default off)."""
         self.model, self.opt, self.ex = model, optimizer, exchange
         fused = self._fused = isinstance(optimizer, FusedAdam)
+        # the task the optimizer was built for (FusedAdam remembers model.f_type; a torch optimizer's filter(requires_grad) followed it)
+        self.task = (optimizer.task if fused else model.f_type) or "caption"
+        self._asked = (bool(use_graph), bool(launch_list))
+        self._check_task(self.task)
         if keep_weight_grads is not None and fused:
             optimizer.set_keep_grads(bool(keep_weight_grads))
         model._unit_loss_grad = True
@@ -61,8 +66,39 @@ class CaptionTrainer:
         # single GPU, FusedAdam, bf16: every weight matrix is stepped in the epilogue of its own weight-gradient GEMM (FusedAdam.
         # enable_dw_fusion); the hook is installed only WHILE this trainer enqueues a step (a plain loss.backward() outside it must
         # keep producing gradients and nothing else)
-        self.fuse_adam = bool(single and optimizer.fuse_dw_default
+        # (match / cross: off -- cross scales the gradients before they are consumed, match gains nothing worth the risk)
+        self.fuse_adam = bool(single and optimizer.fuse_dw_default and self.task == "caption"
                               and model._ps.compute_dtype == torch.bfloat16 and model.flat_grads.is_cuda)
+
+    def _check_task(self, task):
+        """The matching task runs on the eager executor of one process: refuse the rest loudly, before any device work."""
+        if task not in ("match", "cross"):
+            return
+        self.model.check_task(task)
+        if self._asked[0] or self._asked[1]:
+            raise NotImplementedError(f"task {task!r} runs on the eager executor only: use_graph / launch_list recordings of it are not built")
+        if self.ex is not None and self.ex.active:
+            raise NotImplementedError(f"task {task!r} is single-process only: the gradient exchange of it is not built")
+
+    def _step_task(self, feats, mask, ids, text_feats):
+        """match / cross: train_step_kernels_* then the optimizer over the task's range (gradients stay valid: model.grads_valid)."""
+        m = self.model
+        if text_feats is None:
+            raise ValueError(f"task {self.task!r}: pass text_feats (fp32 [B, {m.text_encoder.dim}] on the model's device)")
+        ops.tap("step", 0)
+        if not self._fused:
+            m._ps.masters_written()
+        else:
+            m._ps.refresh_shadow()
+        if self.task == "match":
+            out = m.train_step_kernels_match(feats, mask, text_feats)
+        else:
+            out = m.train_step_kernels_cross(feats, mask, ids, text_feats)
+        self.opt.step()
+        if m.training and m.video_encoder.cfg["dropout"] > 0:
+            ops.advance_seed(m._seed)
+        ops.tap("step", 1)
+        return out
 
     # A/B switch (single GPU): the whole Adam pass after the joined backward instead of 86 % of it beside the encoder backward
     adam_after_backward = os.environ.get("VCT_ADAM_TAIL", "0") == "1"
@@ -218,11 +254,18 @@ class CaptionTrainer:
             return None
         return graph, loss
 
-    def step(self, feats, mask, ids: torch.Tensor) -> torch.Tensor:
-        """Returns this rank's loss as a device tensor [1] (no host sync).  feats / mask: a tensor (one modality), or one tensor
-        per modality (mask: that list or None)."""
+    def step(self, feats, mask, ids: torch.Tensor, text_feats: Optional[torch.Tensor] = None):
+        """Returns this rank's loss as a device tensor [1] (no host sync); the cross task: (loss, cap_loss, match_loss).  feats / mask:
+        a tensor (one modality), or one tensor per modality (mask: that list or None).  text_feats (match / cross): fp32
+        [B, text_encoder.dim]; ids may be None for the match task."""
+        task = self.model.f_type or "caption"
+        if task != self.task:
+            raise ValueError(f"model.mode({task!r}) but the optimizer was built for {self.task!r}: build the optimizer after model.mode(task)")
         if self._fused:
             self.opt.sync_hyper()
+        if task != "caption":
+            self._check_task(task)
+            return self._step_task(feats, mask, ids, text_feats)
         if not (self.use_graph or self.use_list):
             return self._step_kernels(feats, mask, ids)
         self._check_generation()
@@ -250,31 +293,46 @@ class CaptionTrainer:
         return loss
 
 
+def _to_device(model, v_feats, v_masks):
+    dev = model.flat_params.device
+    if model.video_encoder.num_modal > 1:      # every modality (MMEncoder.forward takes the lists)
+        feats = [f.to(dev, non_blocking=True) for f in v_feats]
+        mask = [m.to(dev, non_blocking=True) for m in v_masks] if v_masks is not None else None
+    else:
+        feats = v_feats[0].to(dev, non_blocking=True)
+        mask = v_masks[0].to(dev, non_blocking=True) if v_masks is not None else None
+    return feats, mask
+
+
 def train_epoch(model, optimizer, dataloader, mode: str = "caption", exchange: Optional[GradExchange] = None,
-                log_every: int = 0):
-    """reference train.py:113-148 for mode != 'cross'.  `dataloader` yields (v_feats, v_masks, captions, vids)
-    with the reference's layouts (lists of tensors; captions = id rows or strings).  Returns the epoch-mean of
-    the all-rank mean loss -- one device->host sync per epoch instead of one per step."""
-    if mode != "caption":
-        raise NotImplementedError("only the caption task is on the accelerated path")
+                log_every: int = 0, text_feats_fn=None):
+    """reference train.py:113-148.  `dataloader` yields (v_feats, v_masks, captions, vids) with the reference's layouts (lists of
+    tensors; captions = id rows or strings).  Returns the epoch-mean of the all-rank mean loss ('caption', 'match': a float;
+    'cross': (loss, cap_loss, match_loss)) -- one device->host sync per epoch instead of one per step.
+    text_feats_fn(captions, vids) -> fp32 [B, text_encoder.dim] (match / cross); without it model.text_encoder(captions)."""
+    if mode not in ("caption", "match", "cross"):
+        raise ValueError(f"unknown task {mode!r}")
     model.train()
     model.mode(mode)
     trainer = CaptionTrainer(model, optimizer, exchange)
     dev = model.flat_params.device
-    total = torch.zeros(1, device=dev)
+    total = torch.zeros(3 if mode == "cross" else 1, device=dev)
     n = 0
-    n_modal = model.video_encoder.num_modal
-    for v_feats, v_masks, captions, _vids in dataloader:
-        if n_modal > 1:      # every modality (MMEncoder.forward takes the lists)
-            feats = [f.to(dev, non_blocking=True) for f in v_feats]
-            mask = [m.to(dev, non_blocking=True) for m in v_masks] if v_masks is not None else None
+    for v_feats, v_masks, captions, vids in dataloader:
+        feats, mask = _to_device(model, v_feats, v_masks)
+        if mode == "caption":
+            ids, _ = model.cap_preprocessor(captions)
+            total += trainer.step(feats, mask, ids)
         else:
-            feats = v_feats[0].to(dev, non_blocking=True)
-            mask = v_masks[0].to(dev, non_blocking=True) if v_masks is not None else None
-        ids, _ = model.cap_preprocessor(captions)
-        total += trainer.step(feats, mask, ids)
+            text = text_feats_fn(captions, vids) if text_feats_fn is not None else model.text_encoder(captions)
+            text = text.to(dev, non_blocking=True) if torch.is_tensor(text) else text
+            ids = model.cap_preprocessor(captions)[0] if mode == "cross" else None
+            out = trainer.step(feats, mask, ids, text)
+            total += torch.cat(out) if mode == "cross" else out
         n += 1
     if exchange is not None and exchange.world > 1:
         dist.all_reduce(total, op=dist.ReduceOp.SUM, group=exchange.group)
         total /= exchange.world
+    if mode == "cross":
+        return tuple(v / max(n, 1) for v in total.tolist())
     return float(total) / max(n, 1)
