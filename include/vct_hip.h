@@ -701,6 +701,9 @@ int vct_decode_ln2(int M, int K, const float* x, int64_t ldx, const float* g1, c
  * The input vector of every launch is built by each workgroup: the embedded token (id / table / pos_row) or
  * res + res_bias + sum_c part[c] (the previous block's residual, the bias of its second product, its partial vectors),
  * followed by LayerNorm(g1, b1) and LayerNorm(g2, b2) when given; x_out receives it (the next block's residual).
+ * res is REQUIRED whenever id is absent (res_bias and part stay optional; part alone is VCT_E_ARG): the kernels load it
+ * unconditionally.  res, res_bias, part, table and pos_row are read as 16-byte vectors: one that is given and not 16-byte
+ * aligned is VCT_E_ALIGN.  n_part <= 32 partial vectors (else VCT_E_SHAPE); g2 / b2 only together with g1 / b1.
  * replaces: CapDecoder.decode_word for one caption (model/CapDecoder.py:62-79; torch nn/modules/transformer.py:1143-1199) --
  * 3 launches per layer instead of the 6 of vct_decode_gemv.  w_a / b_a: the first product's weight rows [*, d] and bias
  * (in_proj | q rows | linear1 | generator); w_b: the second product's weight TRANSPOSED, [*, d] = [in, out] (out_proj^T |
@@ -719,7 +722,7 @@ typedef struct vct_decode_block_desc {
   const void* w_b; int64_t ld_b;
   float* part_out;
   /* kind 3 only, optional (sel_ws != NULL): the greedy selection of vct_greedy_select for this ONE caption inside the generator
-   * launch -- every workgroup leaves its (max, first index) pair in sel_ws (fp32 [2 * ceil(V / 128) + 1], zero-initialised once:
+   * launch -- every workgroup leaves its (max, first index) pair in sel_ws (fp32 [2 * ceil(V / 128) + 1], 8-byte aligned (else VCT_E_ALIGN), zero-initialised once:
    * the last word is a ticket counter the launch leaves at zero), the last one to finish writes tok_out[0] and the end-of-sequence
    * bookkeeping (ended[0], ended_count, all_ended_at = min(., t)). */
   float* sel_ws; int64_t* tok_out; int64_t end_id; uint8_t* ended; int32_t* ended_count; int64_t* all_ended_at; int32_t t, pad1;

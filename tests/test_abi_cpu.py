@@ -143,6 +143,60 @@ def test_layer_ss_entry_points_validate_arguments(lib_path):
     assert lib.vct_adam_step_pk(p, p, p, p, p, 8, 1e-3, 0.9, 0.999, 1e-8, 0.0, p, 0, 0, 0, None, None, -1, 0, None) == -1
 
 
+def test_decode_block_entry_refuses_before_any_launch(lib_path):
+    """vct_decode_block (csrc/vct_decode_block.hip): unsupported shapes, a missing res, LayerNorm 2 without LayerNorm 1 and
+    misaligned vector inputs are codes.  Dummy host pointers; every descriptor also carries a later refusal with ANOTHER code
+    (null part_out: VCT_E_ARG; generator with V = 0: VCT_E_SHAPE), so a missing check shows as the wrong code, not as a launch."""
+    from vct_amd import _lib
+    lib = _lib.load()
+    ARG, SHAPE, ALIGN = -1, -2, -3
+    raw = (ctypes.c_char * 8192)()
+    p = (ctypes.addressof(raw) + 15) & ~15          # 16-byte aligned; p + 4 is not, p + 8 is 8- but not 16-byte aligned
+
+    def call(kind, **kw):
+        q = _lib.DecodeBlockDesc()
+        q.kind, q.d, q.ff, q.V, q.Lk = kind, 512, 64, 127, 1
+        q.res, q.w_a, q.ld_a, q.b_a, q.w_b, q.ld_b = p, p, 512, p, p, 512
+        q.slot, q.kc, q.vc, q.kv_ld = p, p, p, 1536
+        q.part_out = None
+        for k, v in kw.items():
+            setattr(q, k, v)
+        return lib.vct_decode_block(q, None)
+    assert lib.vct_decode_block(None, None) == ARG and call(4) == ARG and call(-1) == ARG
+    assert call(2) == ARG                                                       # (the guard itself: null part_out)
+    # shapes
+    assert call(2, part=p, n_part=33) == SHAPE and call(2, part=p, n_part=32) == ARG
+    assert call(2, ff=2112) == SHAPE and call(2, ff=96) == SHAPE and call(2, ff=0) == SHAPE and call(2, ff=2048) == ARG
+    for kind in (0, 1):
+        assert call(kind, Lk=0) == SHAPE and call(kind, Lk=65) == SHAPE and call(kind, Lk=64) == ARG
+    for kind in range(4):
+        assert call(kind, d=768) == SHAPE and call(kind, d=0) == SHAPE
+    assert call(3, V=0, part_out=p) == SHAPE and call(3, V=-5, part_out=p) == SHAPE
+    # the input vector: res is required whenever id is absent (the kernels load it unconditionally) ...
+    guard = dict(V=0, part_out=p)                                               # generator with V = 0: VCT_E_SHAPE at the very end
+    assert call(3, res=None, **guard) == ARG
+    assert call(3, res=None, part=p, n_part=8, **guard) == ARG                  # (partial vectors alone were accepted before)
+    assert call(3, res=None, res_bias=p, **guard) == ARG
+    assert call(3, id=p, res=None, **guard) == ARG and call(3, id=p, table=p, res=None, **guard) == ARG     # id needs table and pos_row
+    assert call(3, id=p, table=p, pos_row=p, res=None, **guard) == SHAPE        # a complete embed source passes on to the guard
+    # ... LayerNorm parameters come in pairs, the second only after the first
+    assert call(3, g2=p, b2=p, **guard) == ARG and call(3, g1=p, **guard) == ARG and call(3, g1=p, b1=p, g2=p, **guard) == ARG
+    assert call(3, g1=p, b1=p, g2=p, b2=p, **guard) == SHAPE
+    # ... and every vector input is read as 16-byte loads
+    for off in (4, 8):
+        assert call(2, res=p + off) == ALIGN
+        assert call(2, res_bias=p + off) == ALIGN
+        assert call(2, part=p + off, n_part=8) == ALIGN
+        assert call(2, id=p, table=p + off, pos_row=p) == ALIGN
+        assert call(2, id=p, table=p, pos_row=p + off) == ALIGN
+    assert call(2, res_bias=p, part=p, n_part=8) == ARG                         # all aligned: on to the guard
+    # the selection workspace holds 8-byte pairs
+    sel = dict(tok_out=p, ended=p, ended_count=p, all_ended_at=p, t=3)
+    assert call(3, sel_ws=p + 4, **sel) == ALIGN and call(3, sel_ws=p + 8, **sel) == ARG
+    assert call(3, sel_ws=p, tok_out=p, ended=p, ended_count=p, t=3, **guard) == ARG     # selection without all_ended_at
+    assert call(3, sel_ws=p, **sel, **guard) == SHAPE
+
+
 def test_no_cpu_fallback_when_library_is_missing(monkeypatch, lib_path):
     from vct_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)

@@ -351,3 +351,40 @@ def test_batch1_decode_with_wide_feedforward_falls_back():
     finally:
         engine.DecoderEngine.block_decode = old
     assert torch.equal(ys, ys2) and ys.shape[1] >= 2
+
+
+@pytest.mark.parametrize("path", ["block", "gemv"])
+def test_batch1_decode_at_the_key_count_limit(path, monkeypatch):
+    """Both batch-1 steps at the limit their predicates admit: 63 frames (64 memory rows) and a 64-position session, teacher-forced
+    along random ids through all 63 positions (self-attention over 1 .. 63 keys, cross-attention over 64).  Every position's
+    logits against the oracle's decode_word under the bf16 bound of test_cfgB_bf16_kv_cache_step_teacher_forced; no margin
+    filter, nothing left out."""
+    from vct_amd import decode, engine
+    if path == "gemv":
+        monkeypatch.setattr(engine.DecoderEngine, "block_decode", False)
+    mc = {"modal": ["clip"], "modal_shape": [512], "text_enc_type": "CLIP", "embed_dim": 512, "dropout": 0.3, "loss_beta": 0.5,
+          "matching": None, "activation": "gelu",
+          "video_encoder": {"layer": 1, "nhead": 8, "feedforward": 2048,
+                            "mme": {"temporal": "encoding", "modal_different": True, "do_norm": False, "aggregation": "avg"}},
+          "caption_decoder": {"layer": 2, "nhead": 8, "feedforward": 2048, "sce_loss_alpha": 0.5}, "pretrained_model": None}
+    V, T, steps = 1009, 63, 63
+    cfg = O.cfg_from_model_config(mc, V)
+    p = O.init_params(cfg, seed=17)
+    f = O.synthetic_batch(1, T, 512, 20, V, seed=9)[0]
+    ids = np.random.default_rng(4).integers(1, V, (1, steps + 1)).astype(np.int64)
+    m = build_model(mc, V, DEV, torch.bfloat16, p)
+    m.eval()
+    dec = m.cap_decoder._engine()
+    st = engine.DecodeState(dec, 1, T + 1, steps + 1)
+    assert (st.Te, st.Lmax) == (64, 64)
+    assert engine._decoder_block_decode_ok(dec, st) == (path == "block") and engine._decoder_small_decode_ok(dec, st)
+    assert engine.decode_step_variant(dec, st) == path
+    feats = torch.from_numpy(f).to(DEV)
+    assert decode.memory_len(feats) == T + 1
+    _, lg = decode.teacher_forced_next_ids(m, feats, None, torch.from_numpy(ids).to(DEV), steps, return_logits=True)
+    assert lg.shape == (1, steps, V) and bool(torch.isfinite(lg).all())
+    mem = O.mm_encoder_forward(p, cfg, f, None)[0]
+    assert mem.shape[1] == T + 1
+    errs = [rel(lg[:, t - 1], O.decode_word(p, cfg, mem, ids[:, :t])) for t in range(1, steps + 1)]
+    print(f"[key-count limit] {path}: worst logit error {max(errs):.3e} at position {int(np.argmax(errs)) + 1}")
+    assert max(errs) < 3e-2, (int(np.argmax(errs)) + 1, max(errs))

@@ -279,10 +279,13 @@ __global__ __launch_bounds__(DB_THREADS) void decode_attn_block_kernel(const DbP
     float vf[8];
     unpack8(vraw, vf);
     const bool fresh = NPROJ == 3 && kj == p.Lk - 1;
-    const float pw = kj < p.Lk ? pj[kj] : 0.0f;
+    const bool live = kj < p.Lk;
+    const float pw = live ? pj[kj] : 0.0f;
     float o[8];
+    // a thread past the last key holds a clamped row's values; with no cached key at all (self, Lk = 1) that row is the slot
+    // itself as it was BEFORE this launch, i.e. whatever the buffer held: selected away, not multiplied by zero (0 * NaN)
 #pragma unroll
-    for (int u = 0; u < 8; u++) o[u] = pw * (fresh ? hv[2 * DB_HD + kc8 * 8 + u] : vf[u]);
+    for (int u = 0; u < 8; u++) o[u] = live ? pw * (fresh ? hv[2 * DB_HD + kc8 * 8 + u] : vf[u]) : 0.0f;
 #pragma unroll
     for (int off = 8; off < 64; off <<= 1)
 #pragma unroll
@@ -456,10 +459,13 @@ extern "C" int vct_decode_block(const vct_decode_block_desc* q, void* stream) {
   p.v.res = q->res; p.v.bias = q->res_bias; p.v.part = q->part; p.v.n_part = q->n_part;
   p.v.g1 = q->g1; p.v.b1 = q->b1; p.v.g2 = q->g2; p.v.b2 = q->b2; p.v.x_out = q->x_out;
   if (p.v.id != nullptr && (!p.v.table || !p.v.pos_row)) return VCT_E_ARG;
-  if (p.v.id == nullptr && !p.v.res && !(p.v.part && p.v.n_part > 0)) return VCT_E_ARG;
+  // without an id the kernels load res unconditionally and use it as the stand-in address of every absent input (vec_issue)
+  if (p.v.id == nullptr && !p.v.res) return VCT_E_ARG;
   if ((p.v.g1 == nullptr) != (p.v.b1 == nullptr) || (p.v.g2 == nullptr) != (p.v.b2 == nullptr) || (p.v.g2 && !p.v.g1)) return VCT_E_ARG;
   if (p.v.part == nullptr) p.v.n_part = 0;
   if (p.v.n_part > DB_PMAX) return VCT_E_SHAPE;
+  // the vector's inputs are read as 16-byte loads (absent ones are null: aligned)
+  if (((uintptr_t)q->res | (uintptr_t)q->res_bias | (uintptr_t)q->part | (uintptr_t)q->table | (uintptr_t)q->pos_row) & 15) return VCT_E_ALIGN;
   p.w_in = reinterpret_cast<const bf16_t*>(q->w_a); p.ld_in = q->ld_a; p.b_in = q->b_a;
   p.n_proj = q->kind == 0 ? 3 : 1;
   p.slot = reinterpret_cast<bf16_t*>(q->slot);
@@ -472,6 +478,7 @@ extern "C" int vct_decode_block(const vct_decode_block_desc* q, void* stream) {
   p.tok_out = q->tok_out; p.end_id = q->end_id; p.ended = q->ended; p.ended_count = q->ended_count;
   p.all_ended_at = reinterpret_cast<unsigned long long*>(q->all_ended_at); p.t = q->t;
   if (p.sel_ws != nullptr && (!p.tok_out || !p.ended || !p.ended_count || !p.all_ended_at || q->t < 0)) return VCT_E_ARG;
+  if ((uintptr_t)p.sel_ws & 7) return VCT_E_ALIGN;            // the (value, index) pairs are 8-byte atomics
   if (!q->w_a || !q->b_a || !q->part_out || (q->ld_a % 8) || ((uintptr_t)q->w_a & 15)) return VCT_E_ARG;
   hipStream_t st = (hipStream_t)stream;
   if (q->kind == 0 || q->kind == 1) {
