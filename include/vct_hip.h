@@ -623,6 +623,59 @@ int vct_beam_select(int dtype, int B, int K, int V, const void* x, int64_t ldx, 
 int vct_beam_reorder(int dtype, int L, int M, int Lmax, int d, int t, const int32_t* parent, const void* src, void* dst,
                      int64_t layer_stride, void* stream);
 /* ---------------------------------------------------------------------------------------------
+ * Sampled decoding on the KV-cached decode step (csrc/vct_sample.hip).  The reference has no sampling decoder; the semantics
+ * are the project's (decode.sample_decode_ids).
+ *
+ * vct_sample_select: one selection step for `rows` independent rows: draws one token per row from the softmax of
+ * x * inv_temp over the row's candidates and keeps vct_greedy_select's end bookkeeping.  The settings are READ FROM DEVICE
+ * MEMORY (ctl, 16 bytes, 16-byte aligned), so one captured graph serves every seed / temperature / k / p:
+ *   ctl = { uint32 seed; int32 top_k; float inv_temp; float top_p }      top_k is clamped to [0, min(64, V)] by the kernel
+ * Per row r (x [rows, ldx] bf16 / fp32 logits, V valid columns, ldx >= V):
+ *   ended[r] != 0 before the call: out = pad_id, step_logp = 0, seq_logp and the counters untouched.
+ *   candidates  top_k == 0: all V tokens in index order; top_k >= 1: the min(top_k, V) largest RAW logits in rank order
+ *               (value descending, ties to the smaller index).
+ *   weights     z = float(x) * inv_temp (fp32), m = max z over the candidates, w = exp(z - m).
+ *   nucleus     top_k >= 1 and top_p < 1: the shortest rank-order prefix whose running fp32 sum of w is >= top_p * (sum of
+ *               every candidate's w); at least one candidate is kept.
+ *   draw        W = sum of the kept w; the first kept candidate, in candidate order, whose running sum exceeds u * W (the
+ *               last kept one if rounding leaves none); u = (h >> 8) * 2^-24, h = hash32(hash32(key) + (t * rows + r) *
+ *               0x9E3779B1), key = (seed * 0x9E3779B1) ^ (997 * 0x85EBCA77 + 0x165667B1), all in uint32 (the dropout
+ *               kernels' counter hash at site 997).
+ *   outputs     out[r * out_stride] (int64, column t of the id table) = the token; step_logp[r] = z_c - m - log(W), the
+ *               log-probability under the distribution sampled from; seq_logp[r] += step_logp[r] (one writer per row);
+ *               token == end_id: ended / ended_count / all_ended_at exactly as vct_greedy_select.
+ * Two launches, fixed-order reductions, no floating-point atomics: a second call on the same inputs is bit-identical.
+ * workspace: 16-byte aligned, >= vct_sample_select_workspace_bytes(dtype, rows, V) = rows * CH * (2 + 2 * 64) * 4 bytes,
+ * CH = ceil(V / (256 * (16 / sizeof(dtype)))) (sized for the largest k; else VCT_E_WORKSPACE; 0 for a bad argument).
+ * --------------------------------------------------------------------------------------------- */
+typedef struct vct_sample_ctl {
+  uint32_t seed;
+  int32_t top_k;
+  float inv_temp;
+  float top_p;
+} vct_sample_ctl;
+
+typedef struct vct_sample_select_desc {
+  int32_t dtype;              /* VCT_F32 / VCT_BF16: the logits */
+  int32_t rows, V, t;
+  const void* x;
+  int64_t ldx;
+  int64_t* out;
+  int64_t out_stride;
+  int64_t end_id, pad_id;
+  uint8_t* ended;             /* [rows], sticky */
+  int32_t* ended_count;
+  int64_t* all_ended_at;
+  float* step_logp;           /* [rows], written */
+  float* seq_logp;            /* [rows], += */
+  const vct_sample_ctl* ctl;  /* device memory */
+  void* workspace;
+  int64_t workspace_bytes;
+} vct_sample_select_desc;
+
+int64_t vct_sample_select_workspace_bytes(int dtype, int rows, int V);
+int vct_sample_select(const vct_sample_select_desc* d, void* stream);
+/* ---------------------------------------------------------------------------------------------
  * One stage of the greedy-decode step at SMALL batch (B <= 4): out[b, n] = epilogue(W[n, :] . prologue(...)[b, :]), a weight-
  * streaming matrix-vector kernel whose prologue builds the input vector and whose epilogue finishes the stage, so that the
  * embedding / LayerNorm / attention launches of the per-token step vanish into their consumers (csrc/vct_decode.hip):

@@ -165,6 +165,18 @@ class MatchAggDesc(C.Structure):
                 ("dagg", vp), ("dmem", vp)]
 
 
+class SampleCtl(C.Structure):
+    """include/vct_hip.h, vct_sample_ctl: the settings vct_sample_select reads from device memory."""
+    _fields_ = [("seed", u32), ("top_k", i32), ("inv_temp", f32), ("top_p", f32)]
+
+
+class SampleSelectDesc(C.Structure):
+    """include/vct_hip.h, vct_sample_select_desc: one sampled selection step."""
+    _fields_ = [("dtype", i32), ("rows", i32), ("V", i32), ("t", i32), ("x", vp), ("ldx", i64), ("out", vp), ("out_stride", i64),
+                ("end_id", i64), ("pad_id", i64), ("ended", vp), ("ended_count", vp), ("all_ended_at", vp), ("step_logp", vp),
+                ("seq_logp", vp), ("ctl", vp), ("workspace", vp), ("workspace_bytes", i64)]
+
+
 DEC_PRO = {"none": 0, "embed": 1, "ln": 2, "ln_ln": 3, "self_attn": 4, "cross_attn": 5}
 
 _SIGS = {
@@ -219,6 +231,8 @@ _SIGS = {
     "vct_greedy_select": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, i64, vp, vp, vp, i32, vp]),
     "vct_beam_select": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, vp, vp, vp, i64, i64, i64, vp, vp, i32, vp, i64, vp]),
     "vct_beam_reorder": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, i64, vp]),
+    "vct_sample_select_workspace_bytes": (i64, [C.c_int, C.c_int, C.c_int]),
+    "vct_sample_select": (C.c_int, [C.POINTER(SampleSelectDesc), vp]),
     "vct_gather_pad_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
     "vct_adam_step": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, i64, i64, i32, vp, vp]),
     "vct_adam_step_pk": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, i64, i64, i32, vp, vp, C.c_int, i64, vp]),

@@ -12,11 +12,16 @@ Two implementations with identical results (tests/test_model_gpu.py):
     truncating the id matrix at that step.
 
 Beam search (`beam_decode_ids`, `beam_decode_ids_reference_algorithm`): the reference has none (MMT4Caption.py:186 is a stub,
-predict_video.py:170's `--beam` says "not support yet"); the semantics are stated in `beam_decode_ids`."""
+predict_video.py:170's `--beam` says "not support yet"); the semantics are stated in `beam_decode_ids`.
+
+Sampling (`sample_decode_ids`, `sample_decode_ids_reference_algorithm`): temperature, top-k and nucleus draws, N captions
+per video with their log-probabilities; the reference has none either, the semantics are stated in `sample_decode_ids`."""
+import math
+
 import torch
 
 from . import ops
-from .engine import BeamDecodeState, DecodeState, first_input as _first, memory_len, stage_inputs, static_inputs
+from .engine import SAMPLE_SITE, BeamDecodeState, DecodeState, SampleDecodeState, first_input as _first, memory_len, stage_inputs, static_inputs
 from .utils import capture_graph
 
 
@@ -331,3 +336,173 @@ def beam_decode_ids_reference_algorithm(model, feats: torch.Tensor, mask, beam_s
         if bool(fin.all()):
             break
     return _beam_finish(hist, s, B, K, pre.end_id, length_penalty, return_all), min_margin
+
+
+# ---- sampling ------------------------------------------------------------------------------------------------------------------
+SAMPLE_TOP_K_MAX = 64
+
+
+def _check_sample_args(num_samples, temperature, top_k, top_p):
+    """The range checks of sampled decoding: ValueError before any device work."""
+    if int(num_samples) != num_samples or int(num_samples) < 1:
+        raise ValueError(f"num_samples must be an integer >= 1, got {num_samples}")
+    t = float(temperature)
+    if not math.isfinite(t) or t <= 0.0:
+        raise ValueError(f"temperature must be finite and > 0, got {temperature}")
+    if int(top_k) != top_k or not 0 <= int(top_k) <= SAMPLE_TOP_K_MAX:
+        raise ValueError(f"top_k must be in 0..{SAMPLE_TOP_K_MAX} (0 = the whole vocabulary), got {top_k}")
+    p = float(top_p)
+    if not (0.0 < p <= 1.0):
+        raise ValueError(f"top_p must be in (0, 1], got {top_p}")
+    if p < 1.0 and int(top_k) == 0:
+        raise ValueError("top_p < 1 needs top_k >= 1: the nucleus is taken within the top-k candidates (a nucleus over the whole "
+                         "vocabulary is not implemented and is not approximated silently); pass top_k (at most 64)")
+
+
+def _draw_seed(seed) -> int:
+    """seed=None: one draw from torch's default generator (torch.manual_seed makes a run reproducible); else as given."""
+    if seed is None:
+        return int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+    return int(seed) & 0xFFFFFFFF
+
+
+def _hash32(x: int) -> int:
+    x ^= x >> 16
+    x = (x * 0x85EBCA6B) & 0xFFFFFFFF
+    x ^= x >> 13
+    x = (x * 0xC2B2AE35) & 0xFFFFFFFF
+    return x ^ (x >> 16)
+
+
+def sample_uniforms(seed: int, rows: int, t: int):
+    """The uniforms of step t for rows 0 .. rows-1 (csrc/vct_sample.hip, smp_uniform): the dropout kernels' counter hash at
+    site SAMPLE_SITE, 24 bits each, as Python floats (exact)."""
+    key = (((seed & 0xFFFFFFFF) * 0x9E3779B1) & 0xFFFFFFFF) ^ ((SAMPLE_SITE * 0x85EBCA77 + 0x165667B1) & 0xFFFFFFFF)
+    k = _hash32(key)
+    return [(_hash32((k + ((t * rows + r) & 0xFFFFFFFF) * 0x9E3779B1) & 0xFFFFFFFF) >> 8) / 16777216.0 for r in range(rows)]
+
+
+def _sample_session(model, dec, B, N, Te, max_len) -> SampleDecodeState:
+    cache = model.__dict__.setdefault("_decode_sessions", {})
+    key = ("sample", B, N, Te, max_len, dec.dt)        # never a greedy or beam session's key
+    st = cache.get(key)
+    if st is None:
+        if len(cache) > 3:
+            cache.clear()
+        st = cache[key] = SampleDecodeState(dec, B, N, Te, max_len)
+    return st
+
+
+@torch.no_grad()
+def sample_decode_ids(model, feats: torch.Tensor, mask, max_len: int = 30, num_samples: int = 1, temperature: float = 1.0,
+                      top_k: int = 0, top_p: float = 1.0, seed=None, use_graphs: bool = True, return_logp: bool = False,
+                      sync_every: int = 4, lookahead: int = 3):
+    """Sampled decoding on the KV-cached decode step: N = num_samples captions per video drawn from the model's distribution.
+    Returns ids int64 [B, N, L'] (always three dimensions, L' <= max_len); with return_logp (ids, seq_logp fp32 [B, N]), the
+    sum of the drawn tokens' log-probabilities under the distribution actually sampled from (after temperature / top-k /
+    nucleus), up to and including each row's end token.
+
+    Semantics, per row (B*N independent rows, row b*N + n = sample n of video b) and step t = 1 .. max_len-1, on the step's
+    logits x (bf16 on the bf16 paths): candidates = all V tokens in index order (top_k = 0) or the min(top_k, V) largest raw
+    logits in rank order (value descending, ties to the smaller index; 1 <= top_k <= 64); z = float(x) / temperature in fp32,
+    m = max z over the candidates, w = exp(z - m); with top_p < 1 (needs top_k >= 1: the nucleus is taken WITHIN the top-k
+    candidates) only the shortest rank-order prefix whose running sum of w reaches top_p of the candidates' sum is kept; W =
+    the kept sum; the token is the first kept candidate whose running sum exceeds u * W, its log-probability z - m - log W.
+    u is a stateless 24-bit uniform of (seed, t, row) (sample_uniforms), so a seed reproduces a run bit for bit.  A row that
+    has drawn end_id is ended: it appends pad_id, as a finished beam does.  Stop rule, layout and truncation as greedy's.
+    top_k = 1 is greedy decoding up to and including each row's first end_id.
+
+    seed=None draws one int from torch's default generator.  The settings live in a 16-byte device block that the kernels
+    read, so ONE session and its captured graphs (begin + one per position) serve every seed, temperature, k and p.  The
+    batch-1 block step is greedy-only: samples run on the gemv (B*N = 1), fused (bf16, 2..256 rows) or generic step.
+    ValueError before any device work for an out-of-range setting."""
+    _check_sample_args(num_samples, temperature, top_k, top_p)
+    seed = _draw_seed(seed)
+    dec = model.cap_decoder._engine()
+    B, N = _first(feats).shape[0], int(num_samples)
+    st = _sample_session(model, dec, B, N, memory_len(feats), max_len)
+    st.set_control(seed, int(top_k), float(temperature), float(top_p))
+    stop = _run_session(model, st, feats, mask, max_len, use_graphs, sync_every, lookahead, dec.sample_begin, dec.sample_step)
+    ids = st.ys[:, :stop + 1].clone().view(B, N, stop + 1)
+    if return_logp:
+        # steps that ran past `stop` (lookahead) saw only ended rows: they added nothing
+        return ids, st.seq_logp.clone().view(B, N)
+    return ids
+
+
+def _sample_select_ref(x: torch.Tensor, ended: torch.Tensor, u: torch.Tensor, inv_temp: float, top_k: int, top_p: float,
+                       pad_id: int, delta: float):
+    """Host-side selection of one step in float64 by sample_decode_ids' rule: x fp32 [M, V] -> (tokens, step log-probabilities
+    fp64, undecided bool [M]: the draw was within delta of a candidate's boundary, or a nucleus cut within delta of a running
+    share)."""
+    M, V = x.shape
+    it = torch.tensor(inv_temp, dtype=torch.float32, device=x.device)
+    z = (x.float() * it).double()                                   # the product is rounded to fp32, as on the device
+    if top_k == 0:
+        idx = torch.arange(V, device=x.device)[None, :].expand(M, -1)
+    else:
+        idx = torch.sort(x.float(), dim=1, descending=True, stable=True)[1][:, :min(top_k, V)]
+        z = z.gather(1, idx)
+    m = z.max(1, keepdim=True)[0]
+    w = torch.exp(z - m)
+    cum = torch.cumsum(w, 1)
+    n = cum.shape[1]
+    keep = torch.full((M,), n, dtype=torch.long, device=x.device)
+    cut = torch.full((M,), float("inf"), dtype=torch.float64, device=x.device)
+    if top_k >= 1 and top_p < 1.0:
+        p32 = float(torch.tensor(top_p, dtype=torch.float32))
+        share = cum / cum[:, -1:]
+        keep = (share >= p32).int().argmax(1) + 1
+        cut = (share - p32).abs().min(1)[0]
+    W = cum.gather(1, keep[:, None] - 1)
+    kept = torch.arange(n, device=x.device)[None, :] < keep[:, None]
+    hit = kept & (cum > u[:, None] * W)
+    sel = torch.where(hit.any(1), hit.int().argmax(1), keep - 1)
+    hi = cum.gather(1, sel[:, None]) / W
+    lo = hi - w.gather(1, sel[:, None]) / W
+    margin = torch.minimum(u[:, None] - lo, hi - u[:, None])[:, 0]
+    tok = idx.gather(1, sel[:, None])[:, 0]
+    logp = (z.gather(1, sel[:, None]) - m - torch.log(W))[:, 0]
+    tok = torch.where(ended, torch.full_like(tok, pad_id), tok)
+    logp = torch.where(ended, torch.zeros_like(logp), logp)
+    return tok, logp, (~ended) & ((margin <= delta) | (cut <= delta))
+
+
+@torch.no_grad()
+def sample_decode_ids_reference_algorithm(model, feats: torch.Tensor, mask, max_len: int = 30, num_samples: int = 1,
+                                          temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed=None,
+                                          return_logp: bool = False, delta: float = 1e-5):
+    """sample_decode_ids without the KV cache: every step re-runs the whole decoder (dec.decode_word) on the [B*N, t] histories
+    and selects on the host in torch float64 by the same rule, with the same uniforms.  Returns (result as sample_decode_ids,
+    undecided int64 [B, N]): per row the first step whose decision was within `delta` of a boundary -- the uniform within delta
+    of an end of the chosen candidate's share of [0, 1), or the nucleus cut within delta of a running share -- and max_len where
+    there is none (from that step on a test may not expect the row's ids to agree)."""
+    _check_sample_args(num_samples, temperature, top_k, top_p)
+    seed = _draw_seed(seed)
+    pre = model.cap_preprocessor
+    model._ps.refresh_shadow()
+    model._ps.refresh_lazy_transposed()
+    enc, dec = model.video_encoder._engine(), model.cap_decoder._engine()
+    B, N = _first(feats).shape[0], int(num_samples)
+    M, Te, dev = B * N, memory_len(feats), _first(feats).device
+    mem = enc.forward(feats, mask, False)
+    d = mem.shape[-1]
+    mem_rep = mem.reshape(B, 1, Te, d).expand(-1, N, -1, -1).reshape(M * Te, d).contiguous()
+    inv_temp = float(torch.tensor(1.0 / float(temperature), dtype=torch.float32))
+    hist = torch.full((M, 1), pre.start_id, dtype=torch.long, device=dev)
+    ended = torch.zeros(M, dtype=torch.bool, device=dev)
+    seq = torch.zeros(M, dtype=torch.float64, device=dev)
+    undecided = torch.full((M,), max_len, dtype=torch.long, device=dev)
+    for t in range(1, max_len):
+        logits = dec.decode_word(mem_rep, M, Te, hist).float()
+        u = torch.tensor(sample_uniforms(seed, M, t), dtype=torch.float64, device=dev)
+        tok, logp, und = _sample_select_ref(logits, ended, u, inv_temp, int(top_k), float(top_p), pre.pad_id, delta)
+        undecided = torch.where(und & (undecided == max_len), torch.full_like(undecided, t), undecided)
+        hist = torch.cat([hist, tok[:, None]], 1)
+        seq += logp
+        ended = ended | (tok == pre.end_id)
+        if bool(ended.all()):
+            break
+    ids = hist.view(B, N, -1)
+    res = (ids, seq.float().view(B, N)) if return_logp else ids
+    return res, undecided.view(B, N)

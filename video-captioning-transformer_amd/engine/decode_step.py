@@ -1,4 +1,4 @@
-"""Inference on the KV cache: the state of a greedy / beam decode session, the four variants of the per-token step with their
+"""Inference on the KV cache: the state of a greedy / beam / sampled decode session, the four variants of the per-token step with their
 eligibility tests, and the selection stages.  `eng` is the DecoderEngine whose weights and switches a function works on."""
 import torch
 
@@ -349,3 +349,54 @@ def _decoder_beam_step(eng, st: BeamDecodeState, t: int, end_id: int):
     st.kv_self = list(st.kv_layers[t % 2].unbind(0))
     return _decoder_decode_step_any(eng, st, t, end_id, select=_beam_stage)
 
+
+
+class SampleDecodeState(DecodeState):
+    """Static buffers of one sampled-decode session (B videos, N samples each, Te, Lmax): the greedy session's buffers for
+    M = B*N rows (row b*N + n = sample n of video b) with the memory replicated per sample, as BeamDecodeState replicates it per
+    beam -- but ONE self-attention cache (rows never change parents, so nothing is reordered) -- and the sampling state: ctl,
+    the 16-byte control block {uint32 seed, int32 top_k, float inv_temp, float top_p} that vct_sample_select reads on the
+    device (the captured graphs serve every setting), step_logp fp32 [Lmax, M] (row t: the log-probability of the token drawn
+    at step t, 0 for a row that had ended), seq_logp fp32 [M] (their sum) and the selection workspace."""
+
+    def __init__(self, eng: "DecoderEngine", Bv: int, N: int, Te: int, Lmax: int):
+        super().__init__(eng, Bv * N, Te, Lmax)      # (no attention maps: return_attn is a greedy-decode feature)
+        dev = eng.dev
+        M = Bv * N
+        self.Bv, self.N = Bv, N
+        self.mem_rep = torch.empty(M * Te, eng.cfg["d"], dtype=eng.dt, device=dev)
+        self.ctl = torch.zeros(4, dtype=torch.int32, device=dev)
+        self.step_logp = torch.zeros(Lmax, M, dtype=torch.float32, device=dev)
+        self.seq_logp = torch.zeros(M, dtype=torch.float32, device=dev)
+        nws = ops.sample_select_workspace_bytes(torch.float32, M, eng.V) // 4     # fp32 logits (the gemv step's) need the most
+        self.sel_ws = torch.empty(max(nws, 4), dtype=torch.float32, device=dev)
+        self.pad_id = None
+
+    def set_control(self, seed: int, top_k: int, temperature: float, top_p: float):
+        """Write the settings of the next run into ctl (one 16-byte host -> device copy on the current stream)."""
+        import struct
+        raw = struct.pack("<Iiff", int(seed) & 0xFFFFFFFF, int(top_k), 1.0 / float(temperature), float(top_p))
+        self.ctl.copy_(torch.frombuffer(bytearray(raw), dtype=torch.int32))
+
+
+def _decoder_sample_begin(eng, st: SampleDecodeState, mem: torch.Tensor, start_id: int, pad_id: int):
+    """_decoder_decode_begin on the memory replicated to every sample's row + the sampling state of step 0 (ctl is the
+    caller's: it is written before the replays, not by the captured begin graph)."""
+    d, Te = eng.cfg["d"], st.Te
+    st.mem_rep.view(st.Bv, st.N, Te, d).copy_(mem.reshape(st.Bv, 1, Te, d).expand(-1, st.N, -1, -1))
+    _decoder_decode_begin(eng, st, st.mem_rep, start_id, pad_id)
+    st.pad_id = int(pad_id)
+    st.step_logp.zero_()
+    st.seq_logp.zero_()
+
+
+def _sample_stage(eng, st: SampleDecodeState, logits: torch.Tensor, t: int, end_id: int):
+    """Selection stage of a sampled step: one draw per row (vct_sample_select) into column t, its log-probability into row t
+    of step_logp and onto seq_logp, greedy's end bookkeeping."""
+    ops.sample_select(logits, st.ys[:, t], end_id, st.pad_id, st.ended, st.ended_count, st.all_ended_at, t, st.step_logp[t],
+                      st.seq_logp, st.ctl, st.sel_ws, cols=eng.V)
+
+
+def _decoder_sample_step(eng, st: SampleDecodeState, t: int, end_id: int):
+    """One sampled step: the decode step of M = B*N rows with the sampling selection stage (never the batch-1 block step)."""
+    return _decoder_decode_step_any(eng, st, t, end_id, select=_sample_stage)

@@ -181,6 +181,8 @@ class DecoderEngine(_StackBase):
     def decode_step(self, st, t, end_id, select=None): return _ds._decoder_decode_step_any(self, st, t, end_id, select)
     def beam_begin(self, st, mem, start_id, pad_id): return _ds._decoder_beam_begin(self, st, mem, start_id, pad_id)
     def beam_step(self, st, t, end_id): return _ds._decoder_beam_step(self, st, t, end_id)
+    def sample_begin(self, st, mem, start_id, pad_id): return _ds._decoder_sample_begin(self, st, mem, start_id, pad_id)
+    def sample_step(self, st, t, end_id): return _ds._decoder_sample_step(self, st, t, end_id)
 
     def backward(self, bucket_ready=None, on_dmem_ready=None, join: bool = True) -> torch.Tensor:
         """d(loss) = 1.  Returns d(memory) [B*Te, d].  bucket_ready(kind, layer) is called when a gradient bucket

@@ -11,6 +11,7 @@ from .params import ParamSet, _Buf
 
 ENC_SITE, DEC_SITE, EMB_SITE = 0, 1000, 999
 ENC_IN_SITE = 998  # the Dropout behind the encoder's input LayerNorm (do_norm): below EMB_SITE, above every encoder layer's ENC_SITE + 16 l + 1..4
+SAMPLE_SITE = 997  # the counter hash behind sampled decoding's uniforms (csrc/vct_sample.hip, SMP_SITE): below ENC_IN_SITE, above every encoder layer's sites
 DMEM_SYNC = 0      # named sync point (ops.sync_record / sync_wait): d(memory) is final on the main stream
 
 

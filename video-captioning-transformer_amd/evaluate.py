@@ -14,8 +14,23 @@ def _strip_special(s: str) -> str:
     return s.replace("[CLS]", "").replace("[SEP]", "")          # eval.py:143, train.py:200
 
 
+_SAMPLE_KEYS = ("num_samples", "temperature", "top_k", "top_p", "seed")
+
+
+def _check_sample(sample, beam_size, return_attn):
+    if sample is None:
+        return
+    if beam_size is not None or return_attn:
+        raise ValueError("sample= excludes beam_size and return_attn: sampling is its own decoder and returns no attention maps")
+    unknown = sorted(set(sample) - set(_SAMPLE_KEYS))
+    if unknown:
+        raise ValueError(f"sample= takes {_SAMPLE_KEYS}, got {unknown}")
+
+
 @torch.no_grad()
-def _decode(model, feats, masks, max_len, beam_size, return_attn=False):
+def _decode(model, feats, masks, max_len, beam_size, return_attn=False, sample=None):
+    if sample is not None:
+        return model.sample_decode(feats, masks, max_len=max_len, **sample)
     if beam_size is None:
         return model.greedy_decode(feats, masks, max_len=max_len, return_attn=return_attn)
     return model.beam_decode(feats, masks, beam_size=beam_size, max_len=max_len, return_attn=return_attn)
@@ -33,10 +48,14 @@ def average_attention(maps: torch.Tensor, length: Optional[int] = None) -> torch
 
 @torch.no_grad()
 def v2t_batch(model, video_feats: Sequence[torch.Tensor], video_masks: Optional[Sequence[torch.Tensor]], max_len: int = 30,
-              beam_size: Optional[int] = None, return_attn: bool = False):
+              beam_size: Optional[int] = None, return_attn: bool = False, sample: Optional[dict] = None):
     """eval.py:126-145: video_feats = list (one per modality) of [B, T, E]; masks = list of bool [B, T] or None.
     beam_size: None = greedy (the reference's only mode), else beam search with that many beams (MMT4Caption.beam_decode).
-    return_attn (greedy only): (captions, cross-attention maps fp32 [B, layers, steps, Te]) -- MMT4Caption.greedy_decode_ids."""
+    return_attn (greedy only): (captions, cross-attention maps fp32 [B, layers, steps, Te]) -- MMT4Caption.greedy_decode_ids.
+    sample = dict(num_samples=..., temperature=..., top_k=..., top_p=..., seed=...) (any subset): sampled decoding
+    (MMT4Caption.sample_decode); returns for every video the list of its num_samples captions.  Excludes beam_size and
+    return_attn (ValueError)."""
+    _check_sample(sample, beam_size, return_attn)
     model.eval()
     dev = model.device
     video_feats = [f.to(dev, non_blocking=True) for f in video_feats]
@@ -44,18 +63,24 @@ def v2t_batch(model, video_feats: Sequence[torch.Tensor], video_masks: Optional[
     if return_attn:
         caps, maps = _decode(model, video_feats, video_masks, max_len, beam_size, True)
         return [_strip_special(r) for r in caps], maps
+    if sample is not None:
+        return [[_strip_special(r) for r in caps] for caps in _decode(model, video_feats, video_masks, max_len, None, sample=sample)]
     return [_strip_special(r) for r in _decode(model, video_feats, video_masks, max_len, beam_size)]
 
 
 @torch.no_grad()
 def v2t_single(model, video_feat: Sequence[torch.Tensor], max_len: int = 30, beam_size: Optional[int] = None,
-               return_attn: bool = False):
-    """train.py:194-203: one video (list of [T, E] per modality), no mask.  return_attn: (caption, maps fp32 [layers, steps, Te])."""
+               return_attn: bool = False, sample: Optional[dict] = None):
+    """train.py:194-203: one video (list of [T, E] per modality), no mask.  return_attn: (caption, maps fp32 [layers, steps, Te]).
+    sample (see v2t_batch): the list of the video's num_samples sampled captions."""
+    _check_sample(sample, beam_size, return_attn)
     model.eval()
     feats = [f.unsqueeze(0).to(model.device) for f in video_feat]
     if return_attn:
         caps, maps = _decode(model, feats, None, max_len, beam_size, True)
         return _strip_special(caps[0]), maps[0]
+    if sample is not None:
+        return [_strip_special(r) for r in _decode(model, feats, None, max_len, None, sample=sample)[0]]
     return _strip_special(_decode(model, feats, None, max_len, beam_size)[0])
 
 

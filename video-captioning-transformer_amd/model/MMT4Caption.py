@@ -517,6 +517,37 @@ class MMT4Caption(nn.Module):
         finally:
             self.train(was_training)
 
+    @torch.no_grad()
+    def sample_decode(self, video_feat: List[torch.Tensor], video_masks: Optional[List[torch.Tensor]] = None, num_samples: int = 1,
+                      max_len: int = 30, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed=None,
+                      kv_cache: bool = True) -> List[List[str]]:
+        """Sampled captions: for every video a list of num_samples strings (ids -> text as greedy_decode).  Semantics:
+        decode.sample_decode_ids."""
+        ids = self.sample_decode_ids(video_feat, video_masks, num_samples, max_len, temperature, top_k, top_p, seed, kv_cache)
+        B, N = ids.shape[0], ids.shape[1]
+        flat = self._ids_to_captions(ids.reshape(B * N, -1))
+        return [flat[b * N:(b + 1) * N] for b in range(B)]
+
+    @torch.no_grad()
+    def sample_decode_ids(self, video_feat, video_masks=None, num_samples: int = 1, max_len: int = 30, temperature: float = 1.0,
+                          top_k: int = 0, top_p: float = 1.0, seed=None, kv_cache: bool = True, use_graphs: bool = True,
+                          return_logp: bool = False):
+        """The id table [B, num_samples, <=max_len] of sample_decode (return_logp: (ids, seq_logp fp32 [B, num_samples])).
+        kv_cache=False runs the reference algorithm (full decoder re-run per token, host-side selection with the same draws)."""
+        from .. import decode
+        decode._check_sample_args(num_samples, temperature, top_k, top_p)
+        was_training = self.training
+        self.eval()
+        try:
+            feats, mask = self._video_inputs(video_feat, video_masks)
+            kw = dict(max_len=max_len, num_samples=num_samples, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                      return_logp=return_logp)
+            if kv_cache:
+                return decode.sample_decode_ids(self, feats, mask, use_graphs=use_graphs, **kw)
+            return decode.sample_decode_ids_reference_algorithm(self, feats, mask, **kw)[0]
+        finally:
+            self.train(was_training)
+
     def mode(self, forward_type="caption") -> None:
         self.f_type = forward_type
         matching = getattr(self, "matching", None)

@@ -769,6 +769,26 @@ def beam_reorder(src, dst, parent, M: int, Lmax: int, d: int, t: int):
                                       src.data_ptr(), dst.data_ptr(), src.stride(0), L.stream_ptr()), "vct_beam_reorder")
 
 
+def sample_select_workspace_bytes(dtype, rows: int, V: int) -> int:
+    """Workspace of vct_sample_select (include/vct_hip.h): chunk partials of every row, sized for the largest k (64)."""
+    chunk = 256 * (8 if dtype == torch.bfloat16 else 4)
+    return rows * ((V + chunk - 1) // chunk) * (2 + 2 * 64) * 4
+
+
+def sample_select(x, out, end_id: int, pad_id: int, ended, ended_count, all_ended_at, t: int, step_logp, seq_logp, ctl, ws, cols=None):
+    """One sampled selection step (include/vct_hip.h, vct_sample_select): a token per row drawn from softmax(x * inv_temp) over
+    the row's top-k / nucleus candidates -> `out` (column t of the id table), step_logp written, seq_logp +=, greedy's end
+    bookkeeping.  ctl: the 16-byte device control block {uint32 seed, int32 top_k, float inv_temp, float top_p}."""
+    d = L.SampleSelectDesc()
+    d.dtype, d.rows, d.V, d.t = L.dtype_code(x.dtype), x.shape[0], int(cols or x.shape[1]), int(t)
+    d.x, d.ldx, d.out, d.out_stride = x.data_ptr(), _ld(x), out.data_ptr(), out.stride(0)
+    d.end_id, d.pad_id = int(end_id), int(pad_id)
+    d.ended, d.ended_count, d.all_ended_at = ended.data_ptr(), ended_count.data_ptr(), all_ended_at.data_ptr()
+    d.step_logp, d.seq_logp, d.ctl = step_logp.data_ptr(), seq_logp.data_ptr(), ctl.data_ptr()
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    L.check(L.load().vct_sample_select(L.C.byref(d), L.stream_ptr()), "vct_sample_select")
+
+
 def decode_gemv(W, out, B, *, bias=None, pro="none", x_in=None, ln1=None, ln2=None, embed=None, attn=None, act=None, res=None,
                 out_native=False, ld_out=None, x_out=None, n_valid=None):
     """One stage of the small-batch greedy-decode step (include/vct_hip.h, vct_decode_gemv).  W [N, K]; out: tensor whose row b starts
