@@ -472,6 +472,30 @@ int vct_sce_loss(int dtype, int N, int S, int V, const void* logits, int64_t ldl
                  int64_t ld_dl, float* row_ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sequence-weighted cross-entropy for self-critical sequence training (csrc/vct_wce_loss.hip): vct_sce_loss at alpha = 1 with
+ * one weight (the advantage) per sequence.  The reference has no policy-gradient stage; the semantics are DESIGN.md's.
+ *   row n belongs to sequence b = n / S, label = labels[b*label_batch_stride + n % S], valid when label != pad_id;
+ *   count = number of valid rows;  logp_n = x[y] - max - log(sum exp(x - max)) in fp32
+ *   loss_out[0] = -(sum over valid n of seq_w[b] * logp_n) / count
+ *   tok_logp[n] = logp_n on valid rows, exactly 0 on pad rows                                  (fp32 [N] or NULL)
+ *   dlogits[n, j] = (seq_w[b] / count) * (p_j - [j == y]) on valid rows, exact zeros on pad rows and in columns V..ld_dl-1
+ *   (may alias logits; NULL = forward only).
+ * seq_w: DEVICE fp32 [N / S], read by the kernel (a recording stays valid across steps), or NULL = all ones.  With NULL or with
+ * all 1.0f, loss and dlogits are bitwise those of vct_sce_loss(alpha = 1).  Limits, alignment, the out-of-vocabulary label
+ * (column 0, NaN loss), count == 0, row_ws fp32 [2*N + 2] and the return codes are vct_sce_loss's.  Two calls are bitwise equal
+ * (fixed-order single-workgroup count and finalise, no float atomics).
+ * --------------------------------------------------------------------------------------------- */
+int vct_wce_loss(int dtype, int N, int S, int V, const void* logits, int64_t ldl, const int64_t* labels,
+                 int64_t label_batch_stride, int64_t pad_id, const float* seq_w, float* loss_out, float* tok_logp,
+                 void* dlogits, int64_t ld_dl, float* row_ws, void* stream);
+
+/* out[g*R + r, :] = sum over n < G of in[(g*G + n)*R + r, :] for g < B, r < R: `in` [B*G*R, d] and `out` [B*R, d] contiguous rows
+ * of the compute dtype, 16-byte aligned, d a multiple of 8 (bf16) / 4 (fp32).  fp32 accumulation in ascending n, one rounding into
+ * the compute dtype; G = 1 is a bitwise copy.  Folds d(memory) of G sampled captions per video back onto the video's memory rows.
+ * VCT_E_ARG: bad dtype / NULL; VCT_E_SHAPE: B, G, R, d <= 0 or d not a multiple of the vector; VCT_E_ALIGN: misaligned base. */
+int vct_group_sum(int dtype, int B, int G, int R, int d, const void* in, void* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The video-text matching head (csrc/vct_match.hip), fp32 end to end.
  * replaces: ClipSymmetricalLoss / ClipSymmetricalLoss_WithDualSoftmax (loss.py:7-67) as called by Matching.forward
  * (Matching.py:27-30: loss_fn(text_feat, vid_feat)) and their autograd backward.

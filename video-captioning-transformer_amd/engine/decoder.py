@@ -1,5 +1,6 @@
 """Forward / backward schedule of the caption decoder (training) and its decode entry points."""
 import os
+from typing import Optional
 
 import torch
 
@@ -117,9 +118,17 @@ class DecoderEngine(_StackBase):
         b.t["x_last"] = x
         return self._ln_fwd(b, "nf.", "decoder.norm.", x, None, None)
 
-    def forward(self, mem: torch.Tensor, Bn: int, Te: int, ids: torch.Tensor, training: bool, want_logits=False):
+    def forward(self, mem: torch.Tensor, Bn: int, Te: int, ids: torch.Tensor, training: bool, want_logits=False,
+                seq_w: Optional[torch.Tensor] = None, score: bool = False):
         """mem [B*Te, d] compute dtype; ids int64 [B,S] (pads = pad_id).  Returns (loss[1] fp32, logits or None).
-        The logits gradient is produced in the same pass (in place when logits are not requested)."""
+        The logits gradient is produced in the same pass (in place when logits are not requested).
+
+        seq_w (fp32 [B] on the device, one weight per id row): the self-critical policy-gradient loss
+        -(sum over non-pad tokens of seq_w[row] * log p(token)) / (number of non-pad tokens) with its logits gradient
+        (ops.wce_loss) in place of the SCE loss.  The RCE term and sce_loss_alpha are IGNORED on this path: the policy gradient of
+        an expected reward is -A * grad log p and nothing else.  score=True: forward only (no logits gradient is written; backward()
+        must not follow), unit weights.  Both leave the per-token log-probabilities fp32 [B*(S-1)] (0 on pad rows) in the
+        buffer set as "tok_logp"."""
         pad = self.cfg["pad_id"]
         S = ids.shape[1]
         Sd, M = S - 1, Bn * (S - 1)
@@ -143,10 +152,14 @@ class DecoderEngine(_StackBase):
         logits = b.get("logits", (M, self.Vp), self.dt)
         ops.gemm(y, self.W("generator.weight"), logits, bias=self.F("generator.bias"), n_valid=self.V, tag="gen_fwd")
         loss = b.get("loss", (1,), torch.float32)
-        dlogits = b.get("dlogits", (M, self.Vp), self.dt) if want_logits else logits
+        dlogits = None if score else (b.get("dlogits", (M, self.Vp), self.dt) if want_logits else logits)
         ops.tap("loss", 0)
-        ops.sce_loss(logits, self.V, ids[:, 1:], Sd, pad, self.cfg["sce_loss_alpha"], loss, dlogits,
-                     b.get("row_ws", (2 * M + 2,), torch.float32))
+        if seq_w is not None or score:
+            ops.wce_loss(logits, self.V, ids[:, 1:], Sd, pad, seq_w, loss, dlogits, b.get("row_ws", (2 * M + 2,), torch.float32),
+                         tok_logp=b.get("tok_logp", (M,), torch.float32))
+        else:
+            ops.sce_loss(logits, self.V, ids[:, 1:], Sd, pad, self.cfg["sce_loss_alpha"], loss, dlogits,
+                         b.get("row_ws", (2 * M + 2,), torch.float32))
         ops.tap("loss", 1)
         b.t["dlogits_used"] = dlogits
         if self.attn_maps:

@@ -255,25 +255,34 @@ class MMT4Caption(nn.Module):
         enc = self.video_encoder._engine()
         return enc.ss_bwd_ok()
 
-    def _backward(self, bucket_ready=None, join: bool = True):
+    def _backward(self, bucket_ready=None, join: bool = True, fold=None):
+        """fold = (B, N, Te): the decoder ran on B*N rows over the memory of B videos fanned out N times (_forward_scst) -- its
+        d(memory) [B*N*Te, d] is summed over each video's N blocks (ops.group_sum) on the stream that carries it, before the
+        encoder backward reads it."""
         hook = None
         if bucket_ready is not None:
             def hook(kind, layer=0):
                 bucket_ready(self.bucket_index(kind, layer))
         dec, enc = self.cap_decoder._engine(), self.video_encoder._engine()
+
+        def folded(dmem):      # on the current stream, where d(memory) is final
+            if fold is None:
+                return dmem
+            B, N, Te = fold
+            return ops.group_sum(dmem, enc.cur.get("scst.dmem", (B * Te, dmem.shape[1]), dmem.dtype), B, N, Te)
         if self.overlap_enc_bwd and dec.dev.type == "cuda" and dec.overlap_dw:
             # the encoder's backward only needs d(memory): it runs on the side stream beside the decoder's bottom
             # self-attention backward and the embedding gradient (two chains of small kernels share the chip)
             def launch(dmem, dmem_point, main=False):
                 if main:
-                    enc.backward(dmem, hook, join=False)
+                    enc.backward(folded(dmem), hook, join=False)
                     return
                 side = dec.ensure_side()
                 ops.sync_wait(dmem_point, side)                   # d(memory) final (its last accumulate is on `side` itself)
                 enc.main_stream = torch.cuda.current_stream()     # (EncoderEngine.enc_dw_main: upper layers' weight-gradient groups go there)
                 try:
                     with torch.cuda.stream(side):
-                        enc.backward(dmem, hook)
+                        enc.backward(folded(dmem), hook)
                 finally:
                     enc.main_stream = None
 
@@ -285,7 +294,7 @@ class MMT4Caption(nn.Module):
             dec.backward(hook, on_dmem_ready=on_dmem, join=join)  # join: ends with the main stream joining the side stream
         else:
             dmem = dec.backward(hook)
-            enc.backward(dmem, hook)
+            enc.backward(folded(dmem), hook)
 
     def train_step_kernels(self, feats, mask, ids: torch.Tensor, bucket_ready=None, defer_join: bool = False) -> torch.Tensor:
         """Fast path used by the trainer and bench: forward + backward as one static kernel schedule
@@ -297,6 +306,67 @@ class MMT4Caption(nn.Module):
         opt = self._ps.dw_adam                                # the optimizer epilogue consumed the weight gradients unless told to store them
         self._ps.weight_grads_valid = opt is None or bool(opt.keep_grads)
         return loss
+
+    # ---- self-critical sequence training: N sampled captions per video, one weight (advantage) per caption --------------------
+    def _forward_scst(self, feats, mask, ids, N: int, training, seq_w=None, score=False, want_logits=False):
+        """_forward_loss with the encoder on the B videos and the decoder on the B*N id rows (row b*N + n = sample n of video b, the
+        sampler's layout): the memory rows are copied B -> B*N into an engine buffer (N = 1: used as they are)."""
+        if not self._ps.intact():
+            self._build_flat()
+        self._ps.refresh_shadow()
+        enc, dec = self.video_encoder._engine(), self.cap_decoder._engine()
+        B, Te = first_input(feats).shape[0], memory_len(feats)
+        ops.tap("layers_fwd", 0)
+        if self.overlap_dec_prefix and dec.dev.type == "cuda" and dec.overlap_dw:
+            dec.forward_prefix(B * N, Te, ids, training)
+        mem = self._mem = enc.forward(feats, mask, training)
+        if N > 1:
+            d = mem.shape[1]
+            rep = dec.buf((B * N, Te, ids.shape[1])).get("scst.mem", (B * N * Te, d), mem.dtype)
+            rep.view(B, N, Te, d).copy_(mem.reshape(B, 1, Te, d).expand(-1, N, -1, -1))
+            mem = rep
+        loss, logits = dec.forward(mem, B * N, Te, ids, training, want_logits=want_logits, seq_w=seq_w, score=score)
+        self.cap_decoder._publish_attn(dec)
+        return loss, logits
+
+    def _check_scst_ids(self, feats, ids, num_samples):
+        B, N = first_input(feats).shape[0], int(num_samples)
+        if N < 1:
+            raise ValueError(f"num_samples must be >= 1, got {num_samples}")
+        if ids.dim() != 2 or ids.dtype != torch.int64 or ids.shape[0] != B * N or ids.shape[1] < 2:
+            raise ValueError(f"ids must be int64 [B * num_samples = {B * N}, L >= 2] (row b*N + n = sample n of video b), got "
+                             f"{ids.dtype} {tuple(ids.shape)}")
+        return B, N
+
+    def train_step_kernels_scst(self, feats, mask, ids: torch.Tensor, seq_w: torch.Tensor, num_samples: int = 1) -> torch.Tensor:
+        """The self-critical step as one static kernel schedule, no autograd tape.  feats / mask: B videos (as train_step_kernels);
+        ids int64 [B*N, L], row b*N + n = sample n of video b (sample_decode_ids' layout, pads after each row's end token); seq_w
+        fp32 [B*N] on the device, the advantage of each row.  The encoder runs once on B, its memory is fanned out to the B*N
+        decoder rows, the loss is -(sum over non-pad tokens of seq_w[row] * log p(token)) / (number of non-pad tokens)
+        (DecoderEngine.forward: sce_loss_alpha and the RCE term do not enter), and the decoder's d(memory) is summed over each
+        video's N samples before the encoder backward.  The cross-attention takes no memory mask, so nothing else is fanned out;
+        N = 1 launches neither the copy nor the sum.  Gradients are WRITTEN (not accumulated) into the flat gradient buffer, like
+        train_step_kernels.  Returns the loss tensor [1]."""
+        B, N = self._check_scst_ids(feats, ids, num_samples)
+        if seq_w.dtype != torch.float32 or seq_w.numel() != B * N or seq_w.device != ids.device or not seq_w.is_contiguous():
+            raise ValueError(f"seq_w must be contiguous fp32 [{B * N}] on {ids.device}, got {seq_w.dtype} {tuple(seq_w.shape)} on {seq_w.device}")
+        loss, _ = self._forward_scst(feats, mask, ids, N, self.training, seq_w=seq_w.reshape(-1))
+        self._backward(None, join=True, fold=(B, N, memory_len(feats)) if N > 1 else None)
+        opt = self._ps.dw_adam
+        self._ps.weight_grads_valid = opt is None or bool(opt.keep_grads)
+        return loss
+
+    @torch.no_grad()
+    def score_captions(self, video_feats, video_masks, ids: torch.Tensor, num_samples: int = 1):
+        """Teacher-forced log-probabilities of given captions, forward only (no logits gradient, dropout off, gradient buffers
+        untouched).  ids int64 [B*num_samples, L] (row b*N + n belongs to video b).  Returns (seq_logp fp32 [B*num_samples], the sum
+        over each row's non-pad targets, and tok_logp fp32 [B*num_samples, L-1], log p(ids[:, t+1] | ids[:, :t+1]), 0 where the
+        target is pad)."""
+        feats, mask = self._video_inputs(video_feats, video_masks)
+        B, N = self._check_scst_ids(feats, ids, num_samples)
+        self._forward_scst(feats, mask, ids, N, False, score=True)
+        tok = self.cap_decoder._engine().cur.t["tok_logp"].view(B * N, ids.shape[1] - 1).clone()
+        return tok.sum(1), tok
 
     # ---- reference API -----------------------------------------------------------------------------
     def _video_inputs(self, video_feats, video_masks):

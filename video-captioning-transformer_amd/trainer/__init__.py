@@ -7,4 +7,4 @@ bucket as soon as the backward schedule has enqueued the kernels that complete i
 of the generator gradients (a third of the bytes, ready first) overlaps the rest of backward."""
 from .exchange import GradExchange, ShardedExchange
 from .optim import FusedAdam, build_optimizer
-from .step import CaptionTrainer, train_epoch
+from .step import CaptionTrainer, scst_epoch, train_epoch

@@ -100,6 +100,62 @@ class CaptionTrainer:
         ops.tap("step", 1)
         return out
 
+    def _check_scst(self, num_samples, baseline):
+        """Self-critical training runs on the eager executor of one process, on the caption task: refuse the rest loudly, before
+        any device work."""
+        if self._asked[0] or self._asked[1]:
+            raise NotImplementedError("scst_step runs on the eager executor only: build the trainer without use_graph / launch_list")
+        if self.ex is not None and self.ex.active:
+            raise NotImplementedError("scst_step is single-process only: the gradient exchange of it is not built")
+        if (self.model.f_type or "caption") != "caption" or self.task != "caption":
+            raise ValueError(f"scst_step trains the caption task: model.mode({self.model.f_type!r}), optimizer built for {self.task!r}")
+        if int(num_samples) < 1:
+            raise ValueError(f"num_samples must be >= 1, got {num_samples}")
+        if baseline not in ("mean_others", "greedy"):
+            raise ValueError(f"baseline must be 'mean_others' or 'greedy', got {baseline!r}")
+        if baseline == "mean_others" and int(num_samples) < 2:
+            raise ValueError("baseline 'mean_others' is the leave-one-out mean of the other samples: it needs num_samples >= 2")
+
+    def scst_step(self, feats, mask, reward_fn, vids=None, *, num_samples: int = 5, baseline: str = "mean_others", max_len: int = 30,
+                  temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed=None):
+        """One self-critical sequence training step (policy gradient on a sentence-level reward): sample num_samples captions per
+        video (model.sample_decode_ids, no grad), score them on the host (reward_fn(ids int64 [B, N, L] CPU, vids) -> float [B, N]:
+        the step's one host sync), turn the rewards into advantages (rewards.advantages: 'mean_others' = leave-one-out, 'greedy' =
+        the reward of one greedy_decode caption per video), then model.train_step_kernels_scst on the samples with one advantage
+        per caption, and the optimizer.  The optimizer-in-the-weight-gradient-GEMM fusion stays off for this step.  vids: what
+        reward_fn gets as video ids (default 0 .. B-1).  seed: the sampler's (None: one draw from torch's generator).
+        Returns dict(loss = device tensor [1], reward_mean, baseline_mean = floats, ids = int64 [B, N, L] on the device)."""
+        from ..rewards import advantages
+        import numpy as np
+        self._check_scst(num_samples, baseline)
+        m, N = self.model, int(num_samples)
+        if self._fused:
+            self.opt.sync_hyper()
+            m._ps.refresh_shadow()
+        else:
+            m._ps.masters_written()               # a torch optimizer wrote the fp32 masters: re-cast the shadow before decoding
+        B = first_input(feats).shape[0]
+        vids = list(range(B)) if vids is None else list(vids)
+        ids = m.sample_decode_ids(feats, mask, num_samples=N, max_len=max_len, temperature=temperature, top_k=top_k, top_p=top_p,
+                                  seed=seed)
+        greedy = m.greedy_decode_ids(feats, mask, max_len=max_len) if baseline == "greedy" else None
+        r = np.asarray(reward_fn(ids.cpu(), vids), np.float32)          # the host sync
+        if r.shape != (B, N):
+            raise ValueError(f"reward_fn must return [B = {B}, N = {N}] rewards, got {r.shape}")
+        if greedy is not None:
+            base = np.asarray(reward_fn(greedy.cpu().view(B, 1, -1), vids), np.float32).reshape(B)
+            adv = advantages(r, base)
+        else:
+            adv = advantages(r, "mean_others")
+            base = r - adv
+        seq_w = torch.from_numpy(np.ascontiguousarray(adv.reshape(-1))).to(ids.device)
+        loss = m.train_step_kernels_scst(feats, mask, ids.view(B * N, -1), seq_w, N)
+        self.opt.step()
+        if m.training and m.video_encoder.cfg["dropout"] > 0:
+            ops.advance_seed(m._seed)
+        # (a copy: the engine's loss buffer is rewritten by the next forward, score_captions included)
+        return dict(loss=loss.clone(), reward_mean=float(r.mean()), baseline_mean=float(base.mean()), ids=ids)
+
     # A/B switch (single GPU): the whole Adam pass after the joined backward instead of 86 % of it beside the encoder backward
     adam_after_backward = os.environ.get("VCT_ADAM_TAIL", "0") == "1"
     warm_streams = os.environ.get("VCT_WARM_STREAMS", "1") != "0"
@@ -336,3 +392,21 @@ def train_epoch(model, optimizer, dataloader, mode: str = "caption", exchange: O
     if mode == "cross":
         return tuple(v / max(n, 1) for v in total.tolist())
     return float(total) / max(n, 1)
+
+
+def scst_epoch(model, optimizer, dataloader, reward_fn, **kw):
+    """One epoch of self-critical sequence training (CaptionTrainer.scst_step on every batch): `dataloader` as train_epoch's,
+    reward_fn(ids int64 [B, N, L] CPU, vids) -> float [B, N] (e.g. rewards.CiderD over the training references); **kw: scst_step's
+    keywords (num_samples, baseline, max_len, temperature, top_k, top_p, seed).  Returns (mean loss, mean reward) of the epoch."""
+    model.train()
+    model.mode("caption")
+    trainer = CaptionTrainer(model, optimizer)
+    total = torch.zeros(1, device=model.flat_params.device)
+    reward, n = 0.0, 0
+    for v_feats, v_masks, _captions, vids in dataloader:
+        feats, mask = _to_device(model, v_feats, v_masks)
+        out = trainer.scst_step(feats, mask, reward_fn, vids, **kw)
+        total += out["loss"]
+        reward += out["reward_mean"]
+        n += 1
+    return float(total) / max(n, 1), reward / max(n, 1)
