@@ -496,6 +496,65 @@ int vct_wce_loss(int dtype, int N, int S, int V, const void* logits, int64_t ldl
 int vct_group_sum(int dtype, int B, int G, int R, int d, const void* in, void* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The self-critical reward on the device (csrc/vct_cider.hip): CIDEr-D of sampled token ids against device-resident reference
+ * tables, and the advantages in the layout of vct_wce_loss's seq_w.  The reference has no policy-gradient stage; the semantics
+ * are rewards.CiderD / rewards.advantages, and the tables are built on the host by rewards.CiderD.device_tables().
+ *
+ * Keys.  An n-gram of order k <= VCT_CIDER_MAX_ORDER is four int32 words: its k token ids (>= 0), then -1 padding, so the order
+ * is part of the key.  Keys are compared exactly, word by word; ordered lexicographically as signed words.
+ * Hash of a key (uint32 arithmetic; the numpy builder and the kernel both implement THIS):
+ *     h = 0x811C9DC5;  for each of the four words w, in order:  h = (h ^ (uint32)w) * 0x01000193;
+ *     h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16;        slot = h & (table_cap - 1)
+ * Corpus table: open addressing, linear probing (slot, slot + 1, ... modulo table_cap), table_cap a power of two >= twice the
+ * number of unique corpus n-grams.  Slot s: table_keys[4 * s .. 4 * s + 3] and table_idf[s] = log(#videos) - log(max(1, df)) in
+ * fp64 (the host's own value; the kernel takes no logarithm); an empty slot has key word 0 == -1.  A lookup ends at the key
+ * (found), at an empty slot or after table_cap probes (absent: idf = log_nvid); a collision costs probes, never a score.
+ * Per video v < n_videos (CSR): its references are vid_ref_ptr[v] .. vid_ref_ptr[v + 1] - 1; per reference r: ref_len[r] (tokens
+ * after the cut), ref_norm[4 * r + k] (the norm of order k + 1; 0 beyond n) and its unique n-grams ent_keys / ent_w at
+ * ref_ent_ptr[r] .. ref_ent_ptr[r + 1] - 1, SORTED by key (the kernel searches them by bisection), ent_w = tf * idf in fp64.
+ *
+ * vct_cider_d: one 256-thread workgroup per candidate (b, s), b < B, s < N.  The candidate is ids[b, s, 1 .. L] through the
+ * element strides (column 0 is the start token and is not read), cut after its first end_id (kept); a row without one is taken
+ * whole; nothing behind the end token reaches the score.  A token id outside [0, 2^31) matches no table entry.  Orders 1 .. n:
+ *     c_w = tf(w) * idf(w);  |c|_k = sqrt(sum_w c_w^2);  sim_k(c, r) = sum_w min(c_w, r_w) * r_w / (|c|_k |r|_k)  (skipped when
+ *     either norm is 0), times exp(-(len c - len r)^2 / two_sigma_sq);  reward[b * N + s] = (float)(10 * sum / (n * R)),
+ * R = the video's reference count; R == 0 (or vid_rows[b] outside [0, n_videos)) scores exactly 0.  Everything behind the
+ * integer counts is fp64, every sum runs serially in first-occurrence order of the candidate's n-grams (the host's order), no
+ * floating-point atomics: two calls agree bitwise.
+ * VCT_E_ARG: NULL descriptor / operand; VCT_E_SHAPE: B, N < 1, L < 0 or L > VCT_CIDER_MAX_LEN, n outside 1 .. VCT_CIDER_MAX_ORDER,
+ * table_cap not a power of two, B * N > 2^31 - 1; VCT_E_ALIGN: an fp64 table not 8-byte or a key table not 16-byte aligned.
+ *
+ * vct_scst_advantages: rewards fp32 [B, N] -> adv fp32 [B * N] (may alias rewards), base_out fp32 [B], means fp32 [2] =
+ * {mean reward, mean baseline}.  baseline == NULL (needs N >= 2, else VCT_E_SHAPE): the leave-one-out mean
+ * base = (sum_n r - r) / (N - 1) in fp64, adv = (float)(r - base), base_out[b] = (float)(sum_n r / N) (the mean of the video's N
+ * leave-one-out baselines).  baseline fp32 [B]: adv = (float)((double)r - baseline[b]), base_out[b] = baseline[b].  The means
+ * are fp64 sums over b (of sum_n r, of the baseline) by ONE workgroup in a fixed order, divided by B * N and B, rounded once.
+ * --------------------------------------------------------------------------------------------- */
+#define VCT_CIDER_MAX_LEN 64
+#define VCT_CIDER_MAX_ORDER 4
+typedef struct vct_cider_desc {
+  int32_t B, N, L, n;            /* L: candidate tokens after the start column */
+  const int64_t* ids;            /* [B, N, 1 + L] through the strides below (elements); points at column 0 */
+  int64_t stride_b, stride_n, stride_l;
+  int64_t end_id;
+  double log_nvid, two_sigma_sq;
+  const int32_t* vid_rows;       /* [B]: the table row of each video */
+  int32_t n_videos, table_cap;
+  const int32_t* table_keys;     /* [table_cap, 4] */
+  const double* table_idf;       /* [table_cap] */
+  const int32_t* vid_ref_ptr;    /* [n_videos + 1] */
+  const int32_t* ref_len;        /* [R_total] */
+  const double* ref_norm;        /* [R_total, 4] */
+  const int32_t* ref_ent_ptr;    /* [R_total + 1] */
+  const int32_t* ent_keys;       /* [E_total, 4] */
+  const double* ent_w;           /* [E_total] */
+  float* reward;                 /* [B * N] */
+} vct_cider_desc;
+int vct_cider_d(const vct_cider_desc* d, void* stream);
+int vct_scst_advantages(int B, int N, const float* rewards, const float* baseline, float* adv, float* base_out, float* means,
+                        void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The video-text matching head (csrc/vct_match.hip), fp32 end to end.
  * replaces: ClipSymmetricalLoss / ClipSymmetricalLoss_WithDualSoftmax (loss.py:7-67) as called by Matching.forward
  * (Matching.py:27-30: loss_fn(text_feat, vid_feat)) and their autograd backward.

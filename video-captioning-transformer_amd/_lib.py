@@ -16,7 +16,7 @@ ACT = {"none": 0, None: 0, "gelu": 1, "relu": 2}
 _ERR = {-1: "VCT_E_ARG (null pointer / bad enum)", -2: "VCT_E_SHAPE (unsupported shape)",
         -3: "VCT_E_ALIGN (leading dimension / alignment)", -4: "VCT_E_WORKSPACE (workspace too small)"}
 
-vp, i32, i64, u32, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float
+vp, i32, i64, u32, f32, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_float, C.c_double
 
 
 class GemmAdam(C.Structure):
@@ -177,6 +177,17 @@ class SampleSelectDesc(C.Structure):
                 ("seq_logp", vp), ("ctl", vp), ("workspace", vp), ("workspace_bytes", i64)]
 
 
+CIDER_MAX_LEN, CIDER_MAX_ORDER = 64, 4
+
+
+class CiderDesc(C.Structure):
+    """include/vct_hip.h, vct_cider_desc: CIDEr-D of sampled ids against device-resident reference tables."""
+    _fields_ = [("B", i32), ("N", i32), ("L", i32), ("n", i32), ("ids", vp), ("stride_b", i64), ("stride_n", i64), ("stride_l", i64),
+                ("end_id", i64), ("log_nvid", f64), ("two_sigma_sq", f64), ("vid_rows", vp), ("n_videos", i32), ("table_cap", i32),
+                ("table_keys", vp), ("table_idf", vp), ("vid_ref_ptr", vp), ("ref_len", vp), ("ref_norm", vp), ("ref_ent_ptr", vp),
+                ("ent_keys", vp), ("ent_w", vp), ("reward", vp)]
+
+
 DEC_PRO = {"none": 0, "embed": 1, "ln": 2, "ln_ln": 3, "self_attn": 4, "cross_attn": 5}
 
 _SIGS = {
@@ -220,6 +231,8 @@ _SIGS = {
     "vct_sce_loss": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, i64, f32, vp, vp, i64, vp, vp]),
     "vct_wce_loss": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, i64, vp, vp, vp, vp, i64, vp, vp]),
     "vct_group_sum": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "vct_cider_d": (C.c_int, [C.POINTER(CiderDesc), vp]),
+    "vct_scst_advantages": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
     "vct_warm": (C.c_int, [vp, i64, vp]),
     "vct_cast": (C.c_int, [C.c_int, C.c_int, vp, vp, i64, vp]),
     "vct_argmax_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, vp]),

@@ -599,6 +599,78 @@ def group_sum(src, out, B: int, G: int, R: int):
     return out
 
 
+def check_cider_ids(ids, device=None):
+    """The refusals of ops.cider_d's candidate table, before any launch: int64 [B, N, L] on the GPU (on `device` when given),
+    1 <= L <= 1 + VCT_CIDER_MAX_LEN columns (column 0 is the start token)."""
+    if not torch.is_tensor(ids) or ids.dtype != torch.int64 or ids.dim() != 3:
+        raise ValueError(f"cider_d: ids must be an int64 tensor [B, N, L], got {getattr(ids, 'dtype', type(ids))} {tuple(getattr(ids, 'shape', ()))}")
+    if not ids.is_cuda or (device is not None and ids.device != device):
+        raise ValueError(f"cider_d: ids must live on the reward tables' device, got {ids.device}")
+    B, N, Lc = ids.shape
+    if B < 1 or N < 1 or Lc < 1 or Lc > 1 + L.CIDER_MAX_LEN:
+        raise ValueError(f"cider_d: ids [B >= 1, N >= 1, 1 <= L <= {1 + L.CIDER_MAX_LEN}] (start column + at most {L.CIDER_MAX_LEN} "
+                         f"tokens), got {tuple(ids.shape)}")
+
+
+def cider_d(ids, vid_rows, tab, out=None):
+    """CIDEr-D of sampled ids on the device (include/vct_hip.h, vct_cider_d).  ids: int64 [B, N, L] (any strides, column 0 the
+    start token); vid_rows: int32 [B] table rows; tab: rewards.DeviceCiderD (its device tensors `t` and scalars); out: fp32
+    [B, N] contiguous or None (allocated).  Returns out.  Enqueued on the current stream; no host synchronisation."""
+    check_cider_ids(ids)
+    B, N, Lc = ids.shape
+    if vid_rows.dtype != torch.int32 or tuple(vid_rows.shape) != (B,) or not vid_rows.is_contiguous() or vid_rows.device != ids.device:
+        raise ValueError(f"cider_d: vid_rows must be int32 [B = {B}] on {ids.device}, got {vid_rows.dtype} {tuple(vid_rows.shape)} on {vid_rows.device}")
+    if not 1 <= int(tab.n) <= L.CIDER_MAX_ORDER:
+        raise ValueError(f"cider_d: n-gram orders 1 .. {L.CIDER_MAX_ORDER}, got n = {tab.n}")
+    if out is None:
+        out = torch.empty(B, N, dtype=torch.float32, device=ids.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, N) or not out.is_contiguous() or out.device != ids.device:
+        raise ValueError(f"cider_d: out must be contiguous fp32 [{B}, {N}] on {ids.device}, got {out.dtype} {tuple(out.shape)}")
+    t = tab.t
+    if t["table_keys"].device != ids.device:
+        raise ValueError(f"cider_d: the reward tables live on {t['table_keys'].device}, ids on {ids.device}")
+    d = L.CiderDesc()
+    d.B, d.N, d.L, d.n = B, N, Lc - 1, int(tab.n)
+    d.ids = ids.data_ptr()
+    d.stride_b, d.stride_n, d.stride_l = ids.stride(0), ids.stride(1), ids.stride(2)
+    d.end_id, d.log_nvid, d.two_sigma_sq = int(tab.end_id), float(tab.log_nvid), float(tab.two_sigma_sq)
+    d.vid_rows, d.n_videos, d.table_cap = vid_rows.data_ptr(), int(tab.n_videos), int(tab.table_cap)
+    for k in ("table_keys", "table_idf", "vid_ref_ptr", "ref_len", "ref_norm", "ref_ent_ptr", "ent_keys", "ent_w"):
+        setattr(d, k, t[k].data_ptr())
+    d.reward = out.data_ptr()
+    L.check(L.load().vct_cider_d(d, L.stream_ptr()), "vct_cider_d")
+    return out
+
+
+def scst_advantages(rewards, baseline=None, adv=None, base_out=None, means=None):
+    """Advantages of sampled captions on the device (include/vct_hip.h, vct_scst_advantages).  rewards: fp32 [B, N] contiguous;
+    baseline: fp32 [B] (e.g. the greedy captions' rewards) or None = the leave-one-out mean of the video's other samples
+    (needs N >= 2).  Returns (adv fp32 [B * N] in seq_w's layout, base_out fp32 [B], means fp32 [2] = mean reward, mean baseline);
+    each may be passed in (adv may be rewards' own storage)."""
+    if not torch.is_tensor(rewards) or rewards.dtype != torch.float32 or rewards.dim() != 2 or not rewards.is_cuda or not rewards.is_contiguous():
+        raise ValueError(f"scst_advantages: rewards must be contiguous fp32 [B, N] on the GPU, got {getattr(rewards, 'dtype', type(rewards))} "
+                         f"{tuple(getattr(rewards, 'shape', ()))}")
+    B, N = rewards.shape
+    if B < 1 or N < 1:
+        raise ValueError(f"scst_advantages: rewards [B >= 1, N >= 1], got {tuple(rewards.shape)}")
+    if baseline is None and N < 2:
+        raise ValueError("scst_advantages: the leave-one-out baseline needs num_samples >= 2")
+
+    def buf(x, shape, what):
+        if x is None:
+            return torch.empty(shape, dtype=torch.float32, device=rewards.device)
+        if x.dtype != torch.float32 or x.numel() != shape[0] or not x.is_contiguous() or x.device != rewards.device:
+            raise ValueError(f"scst_advantages: {what} must be contiguous fp32 with {shape[0]} elements on {rewards.device}, "
+                             f"got {x.dtype} {tuple(x.shape)} on {x.device}")
+        return x
+    if baseline is not None:
+        baseline = buf(baseline, (B,), "baseline")
+    adv, base_out, means = buf(adv, (B * N,), "adv"), buf(base_out, (B,), "base_out"), buf(means, (2,), "means")
+    L.check(L.load().vct_scst_advantages(B, N, rewards.data_ptr(), L.ptr(baseline), adv.data_ptr(), base_out.data_ptr(), means.data_ptr(),
+                                         L.stream_ptr()), "vct_scst_advantages")
+    return adv, base_out, means
+
+
 def match_loss_workspace_bytes(B: int, Dt: int) -> int:
     """Bytes of caller-owned workspace ops.match_loss needs (include/vct_hip.h); raises for a shape the kernels do not take."""
     n = int(L.load().vct_match_loss_workspace_bytes(int(B), int(Dt)))

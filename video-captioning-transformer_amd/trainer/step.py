@@ -124,10 +124,20 @@ class CaptionTrainer:
         the reward of one greedy_decode caption per video), then model.train_step_kernels_scst on the samples with one advantage
         per caption, and the optimizer.  The optimizer-in-the-weight-gradient-GEMM fusion stays off for this step.  vids: what
         reward_fn gets as video ids (default 0 .. B-1).  seed: the sampler's (None: one draw from torch's generator).
-        Returns dict(loss = device tensor [1], reward_mean, baseline_mean = floats, ids = int64 [B, N, L] on the device)."""
+        Returns dict(loss = device tensor [1], reward_mean, baseline_mean = floats, ids = int64 [B, N, L] on the device).
+
+        A reward object with `on_device = True` (rewards.CiderD.to_device()) keeps the whole step on the device: reward_fn(ids,
+        vids) is enqueued behind the sampler on the current stream (the greedy baseline is scored by the same kernel on
+        [B, 1, L]), ops.scst_advantages writes seq_w, and the step never copies ids to the host nor waits for the reward.  On
+        THAT path reward_mean and baseline_mean are 0-dim DEVICE tensors (fp32): floats would put the host sync back; convert
+        them when you need the numbers (scst_epoch does it once per epoch).  max_len above 65 is a ValueError there, before any
+        launch (the reward kernel takes the start column + 64 tokens)."""
+        self._check_scst(num_samples, baseline)
+        if getattr(reward_fn, "on_device", False):
+            return self._scst_step_device(feats, mask, reward_fn, vids, int(num_samples), baseline, max_len, temperature, top_k, top_p,
+                                          seed)
         from ..rewards import advantages
         import numpy as np
-        self._check_scst(num_samples, baseline)
         m, N = self.model, int(num_samples)
         if self._fused:
             self.opt.sync_hyper()
@@ -155,6 +165,38 @@ class CaptionTrainer:
             ops.advance_seed(m._seed)
         # (a copy: the engine's loss buffer is rewritten by the next forward, score_captions included)
         return dict(loss=loss.clone(), reward_mean=float(r.mean()), baseline_mean=float(base.mean()), ids=ids)
+
+    def _scst_step_device(self, feats, mask, reward_fn, vids, N, baseline, max_len, temperature, top_k, top_p, seed):
+        """scst_step with a device-resident reward: same stages, nothing on the host between the sampler and the train step."""
+        from ..rewards import DEVICE_MAX_LEN
+        if int(max_len) > 1 + DEVICE_MAX_LEN:
+            raise ValueError(f"scst_step: a device reward scores the start column + at most {DEVICE_MAX_LEN} tokens, got max_len = {max_len}")
+        m = self.model
+        B = first_input(feats).shape[0]
+        vids = list(range(B)) if vids is None else list(vids)
+        if len(vids) != B:
+            raise ValueError(f"scst_step: {B} videos and {len(vids)} video ids")
+        rows = getattr(reward_fn, "video_rows", None)
+        if rows is not None:
+            rows(vids)                            # KeyError for an unknown video, and the id upload, ahead of the sampler's queue
+        if self._fused:
+            self.opt.sync_hyper()
+            m._ps.refresh_shadow()
+        else:
+            m._ps.masters_written()
+        ids = m.sample_decode_ids(feats, mask, num_samples=N, max_len=max_len, temperature=temperature, top_k=top_k, top_p=top_p,
+                                  seed=seed)
+        greedy = m.greedy_decode_ids(feats, mask, max_len=max_len) if baseline == "greedy" else None
+        r = reward_fn(ids, vids)
+        if not torch.is_tensor(r) or tuple(r.shape) != (B, N) or r.dtype != torch.float32 or r.device != ids.device:
+            raise ValueError(f"a device reward_fn must return fp32 [B = {B}, N = {N}] on {ids.device}, got {getattr(r, 'shape', type(r))}")
+        base = reward_fn(greedy.view(B, 1, -1), vids).view(B) if greedy is not None else None
+        seq_w, _, means = ops.scst_advantages(r.contiguous(), base)
+        loss = m.train_step_kernels_scst(feats, mask, ids.view(B * N, -1), seq_w, N)
+        self.opt.step()
+        if m.training and m.video_encoder.cfg["dropout"] > 0:
+            ops.advance_seed(m._seed)
+        return dict(loss=loss.clone(), reward_mean=means[0], baseline_mean=means[1], ids=ids)
 
     # A/B switch (single GPU): the whole Adam pass after the joined backward instead of 86 % of it beside the encoder backward
     adam_after_backward = os.environ.get("VCT_ADAM_TAIL", "0") == "1"
@@ -397,16 +439,19 @@ def train_epoch(model, optimizer, dataloader, mode: str = "caption", exchange: O
 def scst_epoch(model, optimizer, dataloader, reward_fn, **kw):
     """One epoch of self-critical sequence training (CaptionTrainer.scst_step on every batch): `dataloader` as train_epoch's,
     reward_fn(ids int64 [B, N, L] CPU, vids) -> float [B, N] (e.g. rewards.CiderD over the training references); **kw: scst_step's
-    keywords (num_samples, baseline, max_len, temperature, top_k, top_p, seed).  Returns (mean loss, mean reward) of the epoch."""
+    keywords (num_samples, baseline, max_len, temperature, top_k, top_p, seed).  Returns (mean loss, mean reward) of the epoch.
+    With a device reward (reward_fn.on_device, e.g. rewards.CiderD.to_device()) the steps' mean rewards are device scalars: they
+    are accumulated on the device (fp64) and read once, at the end of the epoch."""
     model.train()
     model.mode("caption")
     trainer = CaptionTrainer(model, optimizer)
     total = torch.zeros(1, device=model.flat_params.device)
-    reward, n = 0.0, 0
+    on_device = bool(getattr(reward_fn, "on_device", False))
+    reward, n = (torch.zeros((), dtype=torch.float64, device=model.flat_params.device) if on_device else 0.0), 0
     for v_feats, v_masks, _captions, vids in dataloader:
         feats, mask = _to_device(model, v_feats, v_masks)
         out = trainer.scst_step(feats, mask, reward_fn, vids, **kw)
         total += out["loss"]
         reward += out["reward_mean"]
         n += 1
-    return float(total) / max(n, 1), reward / max(n, 1)
+    return float(total) / max(n, 1), float(reward) / max(n, 1)
