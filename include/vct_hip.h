@@ -455,6 +455,18 @@ int vct_embed_fwd(int dtype, int B, int S, int d, const int64_t* ids, int64_t id
 int vct_embed_bwd(int dtype, int B, int S, int d, int V, const int64_t* ids, int64_t id_batch_stride,
                   int64_t pad_id, const void* dx, float* dtable, int32_t* id_ws, int64_t id_ws_ints, int incremental,
                   const uint32_t* seed, uint32_t site, float p_drop, void* stream);
+/* vct_embed_bwd that ALSO marks the rows it writes in a per-row "live" table (uint8 [V], device; NULL: no table): live[id] = 1 for
+ * every id of the batch that is inside [0, V) and is not pad_id -- exactly the rows that receive a gradient.  The table is never
+ * cleared by a call: it accumulates "every token id any batch has used so far", which is what the optimizer's row-aware pass
+ * (vct_adam_step_ranges_rows) steps.  An id outside [0, V) owns no row, with or without a table.  No reference counterpart. */
+int vct_embed_bwd_live(int dtype, int B, int S, int d, int V, const int64_t* ids, int64_t id_batch_stride,
+                       int64_t pad_id, const void* dx, float* dtable, int32_t* id_ws, int64_t id_ws_ints, int incremental,
+                       const uint32_t* seed, uint32_t site, float p_drop, uint8_t* live, void* stream);
+/* live[r] = 1 when any element of row r of exp_avg_rows, exp_avg_sq_rows or (when not NULL) grad_rows has a bit set, else 0
+ * ([V, d] fp32, contiguous): the table rebuilt from the buffers -- when it is created, after an optimizer state was loaded, after
+ * anything but the row-aware pass stepped the table. */
+int vct_embed_live_rebuild(int32_t V, int32_t d, const float* grad_rows, const float* exp_avg_rows, const float* exp_avg_sq_rows,
+                           uint8_t* live, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Symmetric cross-entropy loss + gradient w.r.t. logits, one workgroup per row, row held in registers
@@ -657,6 +669,20 @@ int vct_adam_step_ranges(float* param, const float* grad, float* exp_avg, float*
                          const vct_adam_range* ranges_dev, int32_t nranges, int32_t total_blocks, float lr, float beta1, float beta2,
                          float eps, float weight_decay, int32_t* step_dev, const float* hyper_dev,
                          const vct_adam_pack_seg* segs_dev, int32_t nseg, void* stream);
+/* vct_adam_step_ranges with an optional per-range row table: rows_dev (device array of nranges entries, or NULL) says for range i
+ * that it lies inside a row-major table whose row 0 starts at flat element `origin`, rows of row_len elements (a multiple of 4),
+ * nrows rows, and live[r] != 0 for every row that has ever had a non-zero gradient or moment (vct_embed_bwd_live /
+ * vct_embed_live_rebuild keep that true).  A row that is not live is neither read nor written: with g = m = v = 0 the update
+ * changes nothing, bit for bit, PROVIDED 1 - lr * weight_decay == 1, eps > 0 and the step size is finite -- checked by the kernel
+ * on the hyper-parameters it reads (hyper_dev when given) in a form that needs no pow(): 0 <= lr <= 1e30, 0 <= beta1 <= 0.9999,
+ * 0 <= beta2 <= 0.99999, eps finite; otherwise the range is stepped densely.  live == NULL, a range with a shadow, or a row_len
+ * that is no multiple of 4: dense.  Elements of the range in front of `origin` or behind row nrows - 1
+ * (alignment padding) are stepped.  Live rows get the bits of vct_adam_step_ranges. */
+typedef struct vct_adam_rows { int64_t origin; int32_t row_len, nrows; const uint8_t* live; } vct_adam_rows;
+int vct_adam_step_ranges_rows(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                              const vct_adam_range* ranges_dev, int32_t nranges, int32_t total_blocks, float lr, float beta1, float beta2,
+                              float eps, float weight_decay, int32_t* step_dev, const float* hyper_dev,
+                              const vct_adam_pack_seg* segs_dev, int32_t nseg, const vct_adam_rows* rows_dev, void* stream);
 int vct_adam_step_2d(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
                      void* shadow_t_bf16, int32_t rows, int32_t cols, int64_t ld_t, float lr, float beta1, float beta2,
                      float eps, float weight_decay, int32_t* step_dev, const float* hyper_dev, void* stream);

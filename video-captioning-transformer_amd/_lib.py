@@ -30,6 +30,10 @@ class AdamRange(C.Structure):
     _fields_ = [("begin", i64), ("end", i64), ("blk0", i32), ("shadow", i32)]
 
 
+class AdamRows(C.Structure):
+    _fields_ = [("origin", i64), ("row_len", i32), ("nrows", i32), ("live", vp)]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [("dtype", i32), ("out_dtype", i32), ("ta", i32), ("tb", i32), ("M", i32), ("N", i32), ("K", i32),
                 ("act", i32), ("A", vp), ("lda", i64), ("B", vp), ("ldb", i64), ("C", vp), ("ldc", i64),
@@ -228,6 +232,8 @@ _SIGS = {
     "vct_axpby": (C.c_int, [vp, vp, f32, vp, f32, i64, vp]),
     "vct_embed_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, vp, vp, vp, u32, f32, vp]),
     "vct_embed_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, i64, vp, vp, vp, i64, C.c_int, vp, u32, f32, vp]),
+    "vct_embed_bwd_live": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, i64, vp, vp, vp, i64, C.c_int, vp, u32, f32, vp, vp]),
+    "vct_embed_live_rebuild": (C.c_int, [i32, i32, vp, vp, vp, vp, vp]),
     "vct_sce_loss": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, i64, f32, vp, vp, i64, vp, vp]),
     "vct_wce_loss": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, i64, vp, vp, vp, vp, i64, vp, vp]),
     "vct_group_sum": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
@@ -252,6 +258,7 @@ _SIGS = {
     "vct_adam_step": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, i64, i64, i32, vp, vp]),
     "vct_adam_step_pk": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, i64, i64, i32, vp, vp, C.c_int, i64, vp]),
     "vct_adam_step_ranges": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, i32, vp]),
+    "vct_adam_step_ranges_rows": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, i32, vp, vp]),
     "vct_adam_step_2d": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i64, f32, f32, f32, f32, f32, vp, vp, vp]),
     "vct_cmdlist_create": (C.c_int, [C.POINTER(vp)]),
     "vct_cmdlist_destroy": (C.c_int, [vp]),

@@ -100,17 +100,21 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(int N, int S, int d, con
 //                order.  ([CLS] sits in every caption: as a 256-thread workgroup among the 4 864 of the first version's
 //                one-workgroup-per-position kernel its chain of scan rounds and row fetches was the whole 44 us.)
 // Bitwise reproducible; the rows to write are zeroed by embed_prep_kernel first.
-__global__ void embed_index_kernel(int N, int S, const int64_t* __restrict__ ids, int64_t id_bstride, int64_t pad_id,
+// live (optional, uint8 [V], never cleared here): live[id] = 1 for exactly the ids whose table row the sum pass writes -- what the
+// optimizer's row-aware pass (vct_adam_step_ranges_rows) steps.  Plain stores of the same value by every thread that sees the id.
+__global__ void embed_index_kernel(int N, int S, int V, const int64_t* __restrict__ ids, int64_t id_bstride, int64_t pad_id,
                                    int32_t* __restrict__ first_pos, int32_t* __restrict__ cnt, int32_t* __restrict__ hdr,
-                                   int32_t* __restrict__ flat_cur) {
+                                   int32_t* __restrict__ flat_cur, uint8_t* __restrict__ live) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n == 0) hdr[1] = N;                       // this call's positions: what the NEXT call's prep kernel zeroes
   if (n >= N) return;
   const int64_t id = ids[(size_t)(n / S) * id_bstride + (n % S)];
-  flat_cur[n] = (int32_t)id;  // position-major copy: the passes behind scan it without an integer division per element
-  if (id == pad_id) return;
+  const bool in_table = id >= 0 && id < V;      // an id outside the table owns no row (and must not index the tables)
+  flat_cur[n] = in_table ? (int32_t)id : -1;    // position-major copy: the passes behind scan it without an integer division per element
+  if (id == pad_id || !in_table) return;
   atomicMin(&first_pos[id], n);
   atomicAdd(&cnt[id], 1);
+  if (live != nullptr) live[id] = 1;
 }
 
 constexpr int EMB_LIGHT_MAX = 8;
@@ -125,7 +129,7 @@ __device__ __forceinline__ void embed_bwd_light(int n, int N, int d, const int32
   const int lane = threadIdx.x & 63;
   if (n >= N) return;
   const int32_t id = flat[n];
-  if (id == pad_id || first_pos[id] != n) return;       // not the owner of this table row
+  if (id < 0 || id == pad_id || first_pos[id] != n) return;   // outside the table / not the owner of this table row
   const int occurrences = cnt[id];
   if (occurrences > EMB_LIGHT_MAX) return;              // the heavy workgroups of this launch own it
   const Dropout dr = make_dropout(seed, site, p_drop);
@@ -647,6 +651,13 @@ __global__ __launch_bounds__(256) void embed_prep_kernel(int V, int d, float* __
 extern "C" int vct_embed_bwd(int dtype, int B, int S, int d, int V, const int64_t* ids, int64_t id_batch_stride,
                              int64_t pad_id, const void* dx, float* dtable, int32_t* id_ws, int64_t id_ws_ints, int incremental,
                              const uint32_t* seed, uint32_t site, float p_drop, void* stream) {
+  return vct_embed_bwd_live(dtype, B, S, d, V, ids, id_batch_stride, pad_id, dx, dtable, id_ws, id_ws_ints, incremental, seed, site, p_drop,
+                            nullptr, stream);
+}
+
+extern "C" int vct_embed_bwd_live(int dtype, int B, int S, int d, int V, const int64_t* ids, int64_t id_batch_stride,
+                                  int64_t pad_id, const void* dx, float* dtable, int32_t* id_ws, int64_t id_ws_ints, int incremental,
+                                  const uint32_t* seed, uint32_t site, float p_drop, uint8_t* live, void* stream) {
   if (!dt_ok(dtype) || !ids || !dx || !dtable || !id_ws) return VCT_E_ARG;
   if (B <= 0 || S <= 0 || d <= 0 || V <= 0) return VCT_E_SHAPE;
   if (d % vec_of(dtype) || d / vec_of(dtype) > 256 || (d % 4) || d > 1024) return VCT_E_SHAPE;   // one 16-byte column chunk per thread
@@ -664,7 +675,8 @@ extern "C" int vct_embed_bwd(int dtype, int B, int S, int d, int V, const int64_
   vct::launch(embed_prep_kernel, dim3(incremental ? 512 : 2048), dim3(256), 0, st, V, d, dtable, first_pos, cnt, flat, hdr,
               incremental ? 1 : 0);
   VCT_CHECK_LAUNCH();
-  vct::launch(embed_index_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, S, ids, id_batch_stride, pad_id, first_pos, cnt, hdr, flat);
+  vct::launch(embed_index_kernel, dim3((N + 255) / 256), dim3(256), 0, st, N, S, V, ids, id_batch_stride, pad_id, first_pos, cnt,
+              hdr, flat, live);
   VCT_CHECK_LAUNCH();
   const int vecb = vec_of(dtype);
   const int slots = 1024 / (d / vecb);

@@ -526,17 +526,46 @@ def embed_fwd(ids, S, table, pos, x, dropout: Drop = None):
 
 _embed_ws = {}
 _embed_ws_retired = []
+_embed_live = {}
 
 
-def embed_bwd(ids, S, pad_id, dx, dtable, dropout: Drop = None, id_ws=None, exclusive: bool = False, on_grow=None):
+def embed_live_table(dtable, create: bool = False):
+    """The per-row "live" table of a gradient table (uint8 [V], owned with its embed_bwd workspace: same key), or None.  Once it
+    exists EVERY embed_bwd into `dtable` marks the rows it writes (live[id] = 1; never cleared), so it holds "every id any batch has
+    used so far" -- what the optimizer's row-aware pass steps (adam_step_ranges with rows).  The table outlives a workspace that had to
+    grow (recordings and range tables bake its address, and a mark stays true for ever); a NEW table starts at zero and is only true
+    after embed_live_rebuild -- its creator's job (trainer.FusedAdam.live_refresh)."""
+    key = (dtable.shape[0], dtable.device, dtable.data_ptr())
+    live = _embed_live.get(key)
+    if live is None and create:
+        live = _embed_live[key] = torch.zeros(dtable.shape[0], dtype=torch.uint8, device=dtable.device)
+    return live
+
+
+def embed_live_rebuild(live, exp_avg_rows, exp_avg_sq_rows, grad_rows=None):
+    """live[r] = any bit set in row r of the moment tables (and the gradient table when given), fp32 [V, d] contiguous."""
+    V, d = exp_avg_rows.shape
+    assert live.numel() >= V and live.dtype == torch.uint8
+    for t in (exp_avg_rows, exp_avg_sq_rows, grad_rows):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (V, d))
+    L.check(L.load().vct_embed_live_rebuild(V, d, L.ptr(grad_rows), exp_avg_rows.data_ptr(), exp_avg_sq_rows.data_ptr(), live.data_ptr(),
+                                            L.stream_ptr()), "vct_embed_live_rebuild")
+
+
+def embed_bwd(ids, S, pad_id, dx, dtable, dropout: Drop = None, id_ws=None, exclusive: bool = False, on_grow=None, live=None):
     """dtable fp32 [V, d] = deterministic scatter-add of the dx rows.  exclusive=True: the caller guarantees that nothing but
     this function writes `dtable` between calls (the single-GPU fast training path: gradients are overwritten every step, never
     accumulated or averaged in place) -- from the second exclusive call on, only the rows the previous call wrote are zeroed
-    (10 MB at cfg-B) instead of all V (62.5 MB).  Any non-exclusive call falls back to the full zero-fill and breaks the chain."""
+    (10 MB at cfg-B) instead of all V (62.5 MB).  Any non-exclusive call falls back to the full zero-fill and breaks the chain.
+    live: uint8 [V] row table to mark (default: the one registered for `dtable`, embed_live_table)."""
     B = ids.shape[0]
     s, site, p = _drop(dropout)
     V = dtable.shape[0]
     incremental = False
+    if live is None:
+        live = embed_live_table(dtable)
+    else:
+        assert live.dtype == torch.uint8 and live.numel() >= V
     if id_ws is None:
         # one workspace per gradient table: it remembers the ids of the LAST call into that table (what the next incremental call
         # zeroes) -- shared between two models it made a replayed step of one zero the rows of the other's batch
@@ -558,9 +587,9 @@ def embed_bwd(ids, S, pad_id, dx, dtable, dropout: Drop = None, id_ws=None, excl
         ent[1] = dtable.data_ptr() if exclusive else None
     else:
         assert id_ws.numel() >= 2 * V + 4 + B * S
-    L.check(L.load().vct_embed_bwd(L.dtype_code(dx.dtype), B, S, dx.shape[1], V, ids.data_ptr(),
-                                   ids.stride(0), int(pad_id), dx.data_ptr(), dtable.data_ptr(), id_ws.data_ptr(), id_ws.numel(), int(incremental),
-                                   s, site, p, L.stream_ptr()), "vct_embed_bwd")
+    L.check(L.load().vct_embed_bwd_live(L.dtype_code(dx.dtype), B, S, dx.shape[1], V, ids.data_ptr(),
+                                        ids.stride(0), int(pad_id), dx.data_ptr(), dtable.data_ptr(), id_ws.data_ptr(), id_ws.numel(),
+                                        int(incremental), s, site, p, L.ptr(live), L.stream_ptr()), "vct_embed_bwd_live")
 
 
 def sce_loss(logits, V, labels, S, pad_id, alpha, loss_out, dlogits, row_ws):
@@ -796,9 +825,11 @@ def adam_step(param, grad, exp_avg, exp_avg_sq, shadow, lr, beta1, beta2, eps, w
             "vct_adam_step")
 
 
-def adam_ranges_table(ranges, device):
+def adam_ranges_table(ranges, device, rows=None):
     """Device table for adam_step_ranges: ranges = sorted [(begin, end, has_shadow)] of flat elements (multiples of 4).
-    Returns (table tensor, entries, workgroups)."""
+    Returns (table tensor, entries, workgroups).  rows = {range index: (origin, row_len, nrows, live uint8 tensor)}: those ranges lie
+    inside a row-major table (row 0 at flat element `origin`) with a per-row live table, and the pass skips the rows that are not
+    live (include/vct_hip.h, vct_adam_rows); the result then carries the device row table (and the live tensors) behind the three."""
     EPB = 4096
     arr = (L.AdamRange * len(ranges))()
     blk = 0
@@ -807,15 +838,30 @@ def adam_ranges_table(ranges, device):
         arr[i].begin, arr[i].end, arr[i].blk0, arr[i].shadow = int(a), int(b), blk, int(bool(sh))
         blk += (b - a + EPB - 1) // EPB
     table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
-    return table, len(ranges), blk
+    if not rows:
+        return table, len(ranges), blk
+    rarr = (L.AdamRows * len(ranges))()
+    for i, (origin, row_len, nrows, live) in rows.items():
+        assert 0 <= i < len(ranges) and not ranges[i][2], "a range with a bf16 shadow is stepped densely: give it no row table"
+        assert row_len > 0 and row_len % 4 == 0 and origin % 4 == 0 and live.dtype == torch.uint8 and live.numel() >= nrows
+        rarr[i].origin, rarr[i].row_len, rarr[i].nrows, rarr[i].live = int(origin), int(row_len), int(nrows), live.data_ptr()
+    rtable = torch.frombuffer(bytearray(bytes(rarr)), dtype=torch.uint8).to(device)
+    return table, len(ranges), blk, rtable, [r[3] for r in rows.values()]
 
 
 def adam_step_ranges(param, grad, exp_avg, exp_avg_sq, shadow, table, lr, beta1, beta2, eps, weight_decay, step_dev, hyper=None, pack=None):
     """vct_adam_step over a LIST of ranges of the WHOLE flat buffers in one launch (table from adam_ranges_table): what is left for a
     separate pass when the weight matrices are stepped inside their weight-gradient GEMMs.  pack = (device table of
-    vct_adam_pack_seg with flat indices, entries) or None.  No step-counter bump."""
-    tab, n, blocks = table
+    vct_adam_pack_seg with flat indices, entries) or None.  No step-counter bump.  A table built with rows skips the rows that are
+    not live (same bits: a skipped row is one the update would not change)."""
+    tab, n, blocks = table[:3]
     pk, nseg = (pack[0].data_ptr(), int(pack[1])) if pack is not None and pack[1] else (0, 0)
+    if len(table) > 3:
+        L.check(L.load().vct_adam_step_ranges_rows(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+                                                   L.ptr(shadow), tab.data_ptr(), int(n), int(blocks), float(lr), float(beta1),
+                                                   float(beta2), float(eps), float(weight_decay), step_dev.data_ptr(), L.ptr(hyper), pk,
+                                                   nseg, table[3].data_ptr(), L.stream_ptr()), "vct_adam_step_ranges_rows")
+        return
     L.check(L.load().vct_adam_step_ranges(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), L.ptr(shadow),
                                           tab.data_ptr(), int(n), int(blocks), float(lr), float(beta1), float(beta2), float(eps),
                                           float(weight_decay), step_dev.data_ptr(), L.ptr(hyper), pk, nseg, L.stream_ptr()),

@@ -55,6 +55,14 @@ class FusedAdam(torch.optim.Optimizer):
         self.range_elems = {}
         self._dw_desc = {}
         self._range_tables = {}
+        # per-row live table of the token embedding (live_refresh): rows no batch has used are skipped by the multi-range pass
+        self._emb = emb
+        self._live = None
+        self._live_stale = True
+        if self.live_rows and ps.flat.is_cuda and ps.g[emb].dim() == 2:
+            # made with the optimizer, so that every embedding backward enqueued or recorded from now on marks its rows, whichever
+            # executor or task issues it
+            self._live = ops.embed_live_table(ps.g[emb], create=True)
 
     def _hyper_now(self):
         g = self.param_groups[0]
@@ -91,6 +99,46 @@ class FusedAdam(torch.optim.Optimizer):
         if bool(on) != bool(self.keep_grads):
             self.keep_grads = bool(on)
             self._dw_desc.clear()            # the cached epilogue descriptors carry the flag
+
+    # ---- never-used token-embedding rows are not stepped ---------------------------------------------------------------------------
+    # A/B switch (VCT_ADAM_LIVE=0: the dense pass).  The embedding table is 30522 x 512 fp32 = 469 MB of the multi-range launch's
+    # 470 MB at 30 B per parameter, and a caption batch gives a gradient to the rows of its own tokens only.  A row that never had one
+    # has g = m = v = 0, which Adam without weight decay leaves as it is bit for bit (include/vct_hip.h, vct_adam_rows): the pass
+    # looks at one flag per row and moves the rows of "every id any batch has used so far" (14 % of the table for bench.py's batch).
+    live_rows = os.environ.get("VCT_ADAM_LIVE", "1") != "0"
+
+    def live_refresh(self):
+        """Make the embedding's live table exist and be true.  CaptionTrainer.step calls it before every fused step, OUTSIDE any
+        recording (the table is device memory the recorded launches read and mark, so recordings replay correctly; the rebuild is a
+        188 MB read and must not be part of one).  Host-only check unless the table is new or something else wrote the moments since
+        the last row-aware pass: load_state_dict, or a dense pass over the table (another executor or task, the switch).
+        model.load_state_dict / checkpoint.load_weights write parameters only -- no moment changes, nothing to rebuild."""
+        if not self.live_rows or self.keep_grads:         # (keep_grads: the pass stays dense, the table is brought up to date when it is used again)
+            return
+        ps = self.model._ps
+        g = ps.g[self._emb]
+        if g.dim() != 2 or not ps.flat.is_cuda:
+            return
+        if self._live is None:
+            self._live = ops.embed_live_table(g, create=True)        # from here on every embed_bwd into g marks its rows
+            self._live_stale = True
+        if self._live_stale:
+            a, (V, d) = self.skip[0], g.shape
+            ops.embed_live_rebuild(self._live, self.exp_avg[a:a + V * d].view(V, d), self.exp_avg_sq[a:a + V * d].view(V, d), g)
+            self._live_stale = False
+
+    def _live_rows_for(self, left):
+        """{index in left: (origin, row_len, rows, live)} for the pieces of the embedding table, or None (dense).  The table is
+        passed on the fused single-GPU path only (this function is reached from the dw_fusion branch of step_range: bf16, no gradient
+        exchange, FusedAdam -- the exchange paths, a torch optimizer and fp32 mode never get here) and not with keep_grads; it must be
+        current (live_refresh).  Whether a zero row really is a no-op under the hyper-parameters of the step is the kernel's
+        decision, taken on the device block."""
+        if not self.live_rows or self.keep_grads or self._live is None or self._live_stale:
+            return None
+        s0, s1 = self.skip
+        V, d = self.model._ps.g[self._emb].shape
+        rows = {i: (s0, d, V, self._live) for i, (lo, hi, sh) in enumerate(left) if not sh and lo >= s0 and hi <= s1}
+        return rows or None
 
     def begin_step(self):
         """Forget the matrices registered by the previous enqueue of a step (the set is rebuilt as the backward is enqueued)."""
@@ -177,14 +225,19 @@ class FusedAdam(torch.optim.Optimizer):
             self.range_elems[(a, b)] = sum(r[1] - r[0] for r in left)        # what this call's launch touches (bench.py: bytes of the bracket)
             table, nseg, pk_parts = ps.adam_pack_table(a, b) if (self.pack_in_adam and ps.packed) else (None, 0, [])
             if left:
-                key = (tuple(left), )
+                rows = self._live_rows_for(left)
+                if rows is None and any(lo < self.skip[1] and hi > self.skip[0] for lo, hi, _sh in left):
+                    self._live_stale = True          # a dense pass over the table: the next live_refresh rebuilds
+                key = (tuple(left), rows is not None)
                 tab = self._range_tables.get(key)
                 if tab is None:
-                    tab = self._range_tables[key] = ops.adam_ranges_table(left, ps.flat.device)
+                    tab = self._range_tables[key] = ops.adam_ranges_table(left, ps.flat.device, rows)
                 ops.adam_step_ranges(ps.flat, ps.gflat, self.exp_avg, self.exp_avg_sq, ps.cflat, tab, lr, b1, b2, eps, wd, self.step_dev,
                                      hyper=self.hyper, pack=(table, nseg) if nseg else None)
             ps.refresh_transposed(a, b, packed_done=pk_parts)
             return
+        if a < self.skip[1] and b > self.skip[0]:
+            self._live_stale = True                  # a dense pass over the embedding table: the next live_refresh rebuilds
         # 2-D weights with an eager transposed shadow inside the range (W_g^T): their own pass writes the transposed copy too
         fused = []
         if bf and self.adam_2d:
@@ -255,6 +308,7 @@ class FusedAdam(torch.optim.Optimizer):
         self.exp_avg.copy_(fused["exp_avg"])
         self.exp_avg_sq.copy_(fused["exp_avg_sq"])
         self.step_dev.fill_(fused["step"])
+        self._live_stale = True       # the moments were written from outside: the live table is rebuilt before the next fused step
         self._gathered_at = None      # (a restored step count says nothing about the other ranks' shards: gather_state() again before a save)
         self.sync_hyper()
 

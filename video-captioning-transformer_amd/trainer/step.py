@@ -361,6 +361,10 @@ class CaptionTrainer:
             raise ValueError(f"model.mode({task!r}) but the optimizer was built for {self.task!r}: build the optimizer after model.mode(task)")
         if self._fused:
             self.opt.sync_hyper()
+        if self.fuse_adam:
+            # the embedding's live-row table exists and is true before the step is enqueued, recorded or replayed (host-only check
+            # unless an optimizer state was loaded or a dense pass ran over the table since the last step)
+            self.opt.live_refresh()
         if task != "caption":
             self._check_task(task)
             return self._step_task(feats, mask, ids, text_feats)
