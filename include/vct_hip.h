@@ -567,6 +567,63 @@ int vct_scst_advantages(int B, int N, const float* rewards, const float* baselin
                         void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Caption metrics for evaluation on the device (csrc/vct_capmetric.hip, csrc/vct_cider.hip): BLEU-1..4 ("closest" reference
+ * length, corpus level), ROUGE-L (beta = 1.2) and CIDEr of decoded token ids, as coco-caption's Bleu(4), Rouge() and Cider()
+ * compute them on tokenised strings (eval.py:42-123 scores through them).  METEOR is absent (Java + WordNet data).  The semantics
+ * are metrics.CaptionMetrics; the tables are built on the host by metrics.CaptionMetrics.device_tables().
+ *
+ * Conventions of all three entry points.  A candidate is ids[c, 1 .. L] through the element strides (column 0 is the start token
+ * and is not read), cut BEFORE its first end_id: the end token is dropped and nothing behind it reaches any output; a row without
+ * one is taken whole; L <= VCT_CIDER_MAX_LEN.  A candidate id outside [0, 2^31) matches nothing.  References carry no start or end
+ * token and may have any length; they are CSR over the video's table row v = vid_rows[c]: references vid_ref_ptr[v] ..
+ * vid_ref_ptr[v + 1] - 1 (the SAME array as vct_cider_desc's), tokens of reference r: ref_tok[ref_tok_ptr[r] .. ref_tok_ptr[r + 1] - 1],
+ * each in [0, 2^31).  A video without references (or a row outside [0, n_videos)) gives an all-zero row everywhere.
+ *
+ * vct_capmetric_counts: one 256-thread workgroup per caption c < C.  counts[12 * c ..] = {len, reflen, correct_1..4, guess_1..4,
+ * lcs_max, 0}:  len = tokens after the cut;  reflen = the reference length minimising (|len_r - len|, len_r) (a tie goes to the
+ * shorter reference; an empty candidate gets the shortest);  guess_k = max(0, len - k + 1);  correct_k = sum over the candidate's
+ * distinct k-grams w of min(count_c(w), max_r count_r(w));  lcs_max = max_r LCS(candidate, reference r).
+ * rouge[3 * c ..] = {prec, rec, F}:  prec = lcs_max / len,  rec = max_r LCS_r / len_r (an empty reference contributes 0),
+ * F = (1 + beta_sq) * prec * rec / (rec + beta_sq * prec) when both are non-zero, else 0; each of prec and rec is ONE fp64 division
+ * of two integers (rec's maximum is found by integer cross-multiplication).  The n-gram counts compare token arrays directly
+ * (wave k holds order k + 1, lane p the instance that starts at token p); the LCS is the bit-parallel row recurrence on one
+ * 64-bit word per wave (lane j holds candidate token j; per reference token, M = ballot(match), U = V & M, V = (V + U) | (V - U)
+ * from all ones; LCS = zero bits among the low len bits of V), the group's waves striding over the references.  All integer
+ * outputs are exact, there is no floating-point atomic and no data-dependent order: two calls agree bitwise.
+ * VCT_E_ARG: NULL descriptor / operand or beta_sq not > 0; VCT_E_SHAPE: C < 1, L < 0 or L > VCT_CIDER_MAX_LEN, n_videos < 0;
+ * VCT_E_ALIGN: ids or rouge not 8-byte, an int32 array not 4-byte aligned.
+ *
+ * vct_cider_d_eval: vct_cider_d's kernel (same descriptor, same tables, same order of every sum) with the cut BEFORE the end token;
+ * writes the un-rounded fp64 score[b * N + s] = 10 * sum / (n * R), and also (float) of it to d->reward when that is not NULL.
+ * Refusals as vct_cider_d (reward may be NULL; score NULL: VCT_E_ARG, not 8-byte aligned: VCT_E_ALIGN).
+ *
+ * vct_capmetric_finish: ONE 256-thread workgroup folds the C rows: int64 sums of {len, reflen, correct_k, guess_k}, fp64 sums of
+ * F and (cider != NULL) of cider[c], thread t taking rows t, t + 256, ..., then a fixed-order tree.  With tiny = 1e-15, small = 1e-9:
+ *     p = 1;  for k = 1..4:  p *= (correct_k + tiny) / (guess_k + small),  Bleu_k = pow(p, 1 / k);
+ *     ratio = (len + tiny) / (reflen + small);  if ratio < 1 every Bleu_k *= exp(1 - 1 / ratio)
+ * out[8] = {Bleu_1, Bleu_2, Bleu_3, Bleu_4, ROUGE_L = mean F, CIDEr = mean cider (0 without), Bleu_4 + ROUGE_L + CIDEr, (double)C}.
+ * VCT_E_ARG: NULL counts / rouge / out; VCT_E_SHAPE: C < 1; VCT_E_ALIGN: an fp64 buffer not 8-byte, counts not 4-byte aligned.
+ * --------------------------------------------------------------------------------------------- */
+#define VCT_CAPMETRIC_COUNT_COLS 12
+typedef struct vct_capmetric_desc {
+  int32_t C, L;                  /* captions; candidate tokens after the start column */
+  const int64_t* ids;            /* [C, 1 + L] through the strides below (elements); points at column 0 */
+  int64_t stride_c, stride_l;
+  int64_t end_id;
+  const int32_t* vid_rows;       /* [C]: the table row of each caption's video */
+  int32_t n_videos, reserved;
+  double beta_sq;
+  const int32_t* vid_ref_ptr;    /* [n_videos + 1] */
+  const int32_t* ref_tok_ptr;    /* [R_total + 1] */
+  const int32_t* ref_tok;        /* [T_total] */
+  int32_t* counts;               /* [C, 12] */
+  double* rouge;                 /* [C, 3] */
+} vct_capmetric_desc;
+int vct_capmetric_counts(const vct_capmetric_desc* d, void* stream);
+int vct_cider_d_eval(const vct_cider_desc* d, double* score, void* stream);
+int vct_capmetric_finish(int C, const int32_t* counts, const double* rouge, const double* cider, double* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The video-text matching head (csrc/vct_match.hip), fp32 end to end.
  * replaces: ClipSymmetricalLoss / ClipSymmetricalLoss_WithDualSoftmax (loss.py:7-67) as called by Matching.forward
  * (Matching.py:27-30: loss_fn(text_feat, vid_feat)) and their autograd backward.

@@ -192,6 +192,16 @@ class CiderDesc(C.Structure):
                 ("ent_keys", vp), ("ent_w", vp), ("reward", vp)]
 
 
+CAPMETRIC_COUNT_COLS = 12
+
+
+class CapMetricDesc(C.Structure):
+    """include/vct_hip.h, vct_capmetric_desc: per-caption BLEU / ROUGE-L statistics of decoded ids against reference token lists."""
+    _fields_ = [("C", i32), ("L", i32), ("ids", vp), ("stride_c", i64), ("stride_l", i64), ("end_id", i64), ("vid_rows", vp),
+                ("n_videos", i32), ("reserved", i32), ("beta_sq", f64), ("vid_ref_ptr", vp), ("ref_tok_ptr", vp), ("ref_tok", vp),
+                ("counts", vp), ("rouge", vp)]
+
+
 DEC_PRO = {"none": 0, "embed": 1, "ln": 2, "ln_ln": 3, "self_attn": 4, "cross_attn": 5}
 
 _SIGS = {
@@ -239,6 +249,9 @@ _SIGS = {
     "vct_group_sum": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "vct_cider_d": (C.c_int, [C.POINTER(CiderDesc), vp]),
     "vct_scst_advantages": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "vct_capmetric_counts": (C.c_int, [C.POINTER(CapMetricDesc), vp]),
+    "vct_cider_d_eval": (C.c_int, [C.POINTER(CiderDesc), vp, vp]),
+    "vct_capmetric_finish": (C.c_int, [C.c_int, vp, vp, vp, vp, vp]),
     "vct_warm": (C.c_int, [vp, i64, vp]),
     "vct_cast": (C.c_int, [C.c_int, C.c_int, vp, vp, i64, vp]),
     "vct_argmax_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, vp]),

@@ -31,7 +31,9 @@ __device__ __forceinline__ int cider_cmp(const CiderKey& a, const CiderKey& b) {
 }
 
 // One workgroup per candidate; wave k holds the n-gram instances of order k + 1, lane p the one that starts at token p.
-__global__ __launch_bounds__(256) void cider_d_kernel(const vct_cider_desc d) {
+// EVAL (vct_cider_d_eval): the candidate is cut BEFORE its first end token and the un-rounded fp64 score is written as well.
+template <bool EVAL>
+__global__ __launch_bounds__(256) void cider_d_kernel(const vct_cider_desc d, double* score) {
 #pragma clang fp contract(off)
   __shared__ int tok[VCT_CIDER_MAX_LEN];
   __shared__ double term[4 * VCT_CIDER_MAX_LEN];
@@ -44,7 +46,7 @@ __global__ __launch_bounds__(256) void cider_d_kernel(const vct_cider_desc d) {
     if (tid < L) v = d.ids[(int64_t)b * d.stride_b + (int64_t)s * d.stride_n + (int64_t)(1 + tid) * d.stride_l];
     const unsigned long long ends = __ballot(tid < L && v == d.end_id);
     tok[tid] = (v < 0 || v > 0x7fffffffLL) ? -2 : (int)v;                 // -2: a word no table key holds (theirs are >= 0 or -1)
-    if (tid == 0) s_len = ends ? __ffsll(ends) : L;                      // the first end token is kept
+    if (tid == 0) s_len = ends ? __ffsll(ends) - (EVAL ? 1 : 0) : L;     // the first end token is kept (reward) / dropped (EVAL)
   }
   __syncthreads();
   const int lc = s_len, k = tid >> 6, p = tid & 63;
@@ -127,7 +129,15 @@ __global__ __launch_bounds__(256) void cider_d_kernel(const vct_cider_desc d) {
       }
     }
   }
-  if (tid == 0) d.reward[c] = (r1 > r0) ? (float)(10.0 * total / (double)(d.n * (r1 - r0))) : 0.0f;
+  if (tid == 0) {
+    if (EVAL) {
+      const double sc = (r1 > r0) ? 10.0 * total / (double)(d.n * (r1 - r0)) : 0.0;
+      score[c] = sc;
+      if (d.reward != nullptr) d.reward[c] = (float)sc;
+    } else {
+      d.reward[c] = (r1 > r0) ? (float)(10.0 * total / (double)(d.n * (r1 - r0))) : 0.0f;
+    }
+  }
 }
 
 // ONE workgroup: thread t takes the videos t, t + 1024, ...; the two means are a fixed-order tree over the threads' fp64 partials.
@@ -174,19 +184,36 @@ __global__ __launch_bounds__(1024) void scst_advantages_kernel(int B, int N, con
 
 using namespace vct;
 
-extern "C" int vct_cider_d(const vct_cider_desc* d, void* stream) {
+// the refusals vct_cider_d and vct_cider_d_eval share, in vct_cider_d's order (reward is optional for the evaluation score)
+static int cider_check(const vct_cider_desc* d, bool need_reward) {
   if (!d) return VCT_E_ARG;
   if (d->B < 1 || d->N < 1 || d->L < 0 || d->L > VCT_CIDER_MAX_LEN || d->n < 1 || d->n > VCT_CIDER_MAX_ORDER) return VCT_E_SHAPE;
   if (d->table_cap < 1 || (d->table_cap & (d->table_cap - 1)) || d->n_videos < 0) return VCT_E_SHAPE;
   if ((int64_t)d->B * d->N > 0x7fffffffLL) return VCT_E_SHAPE;
   if (!d->ids || !d->vid_rows || !d->table_keys || !d->table_idf || !d->vid_ref_ptr || !d->ref_len || !d->ref_norm || !d->ref_ent_ptr ||
-      !d->ent_keys || !d->ent_w || !d->reward)
+      !d->ent_keys || !d->ent_w || (need_reward && !d->reward))
     return VCT_E_ARG;
   if (!(d->two_sigma_sq > 0.0)) return VCT_E_ARG;
   if (((uintptr_t)d->table_idf & 7) || ((uintptr_t)d->ref_norm & 7) || ((uintptr_t)d->ent_w & 7)) return VCT_E_ALIGN;
   if (((uintptr_t)d->table_keys & 15) || ((uintptr_t)d->ent_keys & 15)) return VCT_E_ALIGN;
   if (((uintptr_t)d->ids & 7) || ((uintptr_t)d->vid_rows & 3) || ((uintptr_t)d->reward & 3)) return VCT_E_ALIGN;
-  vct::launch(cider_d_kernel, dim3((unsigned)(d->B * d->N)), dim3(256), 0, (hipStream_t)stream, *d);
+  return VCT_OK;
+}
+
+extern "C" int vct_cider_d(const vct_cider_desc* d, void* stream) {
+  const int rc = cider_check(d, true);
+  if (rc != VCT_OK) return rc;
+  vct::launch(cider_d_kernel<false>, dim3((unsigned)(d->B * d->N)), dim3(256), 0, (hipStream_t)stream, *d, (double*)nullptr);
+  VCT_CHECK_LAUNCH();
+  return VCT_OK;
+}
+
+extern "C" int vct_cider_d_eval(const vct_cider_desc* d, double* score, void* stream) {
+  const int rc = cider_check(d, false);
+  if (rc != VCT_OK) return rc;
+  if (!score) return VCT_E_ARG;
+  if ((uintptr_t)score & 7) return VCT_E_ALIGN;
+  vct::launch(cider_d_kernel<true>, dim3((unsigned)(d->B * d->N)), dim3(256), 0, (hipStream_t)stream, *d, score);
   VCT_CHECK_LAUNCH();
   return VCT_OK;
 }

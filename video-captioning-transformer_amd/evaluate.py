@@ -4,7 +4,8 @@
 decodes a whole split in batches and returns {video id: caption}; `val_epoch` is the teacher-forced validation loss
 (train.py:150-167).  COCO scoring (eval.py:42-123) needs Java + pycocoevalcap, neither of which this image has:
 `make_coco_sample` reshapes the dictionaries exactly as eval.py:24-39 does so that an external scorer can be fed, and
-`score_coco` says why it cannot run here instead of pretending."""
+`score_coco` says why it cannot run here instead of pretending.  `eval_metrics` scores a split with the project's own BLEU-1..4,
+ROUGE-L and CIDEr on the device (metrics.py; no METEOR) and `metric_earlystop_score` is the number metric early stopping watches."""
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -121,6 +122,115 @@ def val_epoch(model, dataloader, mode: str = "caption", text_feats_fn=None):
     if mode == "cross":
         return tuple(v / max(n, 1) for v in total.tolist())
     return float(total) / max(n, 1)
+
+
+def _reference_ids(pre, caption) -> List[int]:
+    """A reference caption as the model's caption preprocessor tokenises it, start and end token stripped."""
+    ids = pre.tokenizer.encode(caption) if isinstance(caption, str) else [int(t) for t in caption]
+    if ids and ids[0] == pre.start_id:
+        ids = ids[1:]
+    if ids and ids[-1] == pre.end_id:
+        ids = ids[:-1]
+    return ids
+
+
+def build_scorer(model, video2caption: Dict[str, List[str]], level: str = "token"):
+    """The device scorer eval_metrics uses, over the references {vid: [caption, ...]} of one split; build it once and pass it as
+    eval_metrics(scorer=...) every epoch.  level "token": ids of the model's tokenizer; "word": metrics.normalize_caption words
+    through a metrics.WordTable (kept on the scorer as `.words`)."""
+    from . import metrics
+    if level == "token":
+        pre = model.cap_preprocessor
+        refs = {vid: [_reference_ids(pre, c) for c in caps] for vid, caps in video2caption.items()}
+        scorer = metrics.CaptionMetrics(refs, end_id=pre.end_id).to_device(model.device)
+        scorer.words = None
+    elif level == "word":
+        words = metrics.WordTable()
+        refs = {vid: [words.encode(c) for c in caps] for vid, caps in video2caption.items()}
+        scorer = metrics.CaptionMetrics(refs).to_device(model.device)
+        scorer.words = words
+    else:
+        raise ValueError(f"level must be 'token' or 'word', got {level!r}")
+    scorer.level = level
+    return scorer
+
+
+def _word_rows(scorer, captions: Sequence[str], device) -> torch.Tensor:
+    """Captions -> the id matrix DeviceCaptionMetrics.add takes: column 0 a start column, the words' ids, then the end id."""
+    rows = [scorer.words.encode(c) for c in captions]
+    width = max(len(r) for r in rows)
+    if width > 64:
+        raise ValueError(f"eval_metrics: a caption of {width} words; the device scorer takes at most 64")
+    host = torch.full((len(rows), 1 + max(width, 1)), scorer.end_id, dtype=torch.long)
+    for i, r in enumerate(rows):
+        host[i, 1:1 + len(r)] = torch.tensor(r, dtype=torch.long)
+    return host.to(device)
+
+
+@torch.no_grad()
+def eval_metrics(model, dataloader, max_len: int = 30, beam_size: Optional[int] = None, level: str = "token", scorer=None,
+                 return_captions: bool = False):
+    """train.py:171-192 / eval.py:156-168 with the scoring on the device: decodes every video a by_video loader yields (greedy, or
+    beam search with beam_size beams) and returns {Bleu_1..4, ROUGE_L, CIDEr, sum} (metrics.py), or (that, {vid: caption} exactly
+    as eval_epoch returns it) with return_captions.
+
+    level "token": the references are the loader's dataset.video2caption tokenised once by the model's caption preprocessor; the
+    decoded id matrix goes straight into the scorer -- no string is built and no id leaves the device.  level "word": captions
+    are decoded to strings and compared as metrics.normalize_caption words, the form coco-caption scores; use it when reporting
+    numbers.  scorer: a build_scorer(model, video2caption, level) result to reuse the reference tables across epochs.
+    Only videos with an entry in the references are scored and counted (an entry with an empty list scores 0 and counts);
+    return_captions still returns every decoded video.
+
+    The `sum` has THREE terms (Bleu_4 + ROUGE_L + CIDEr) where the reference's early-stopping sum adds METEOR as a fourth:
+    METEOR needs Java and WordNet data and is not computed."""
+    if level not in ("token", "word"):
+        raise ValueError(f"level must be 'token' or 'word', got {level!r}")
+    if not 2 <= int(max_len) <= 65:
+        raise ValueError(f"eval_metrics: 2 <= max_len <= 65 (the device scorer takes at most 64 tokens after the start token), got {max_len}")
+    dataset = getattr(dataloader, "dataset", None) or getattr(dataloader, "ds", None)      # torch's DataLoader / data.DeviceLoader
+    if scorer is None:
+        if dataset is None:
+            raise ValueError("eval_metrics: the loader has no dataset to take references from; pass scorer=build_scorer(...)")
+        scorer = build_scorer(model, dataset.video2caption, level)
+    elif getattr(scorer, "level", level) != level:
+        raise ValueError(f"eval_metrics: the scorer was built for level {scorer.level!r}, not {level!r}")
+    model.eval()
+    dev = model.device
+    try:
+        capacity = max(len(dataset), 1)
+    except TypeError:
+        capacity = 1024
+    scorer.begin(capacity)
+    vid2result: Dict[str, str] = {}
+    for v_feats, v_masks, _caps, vids in dataloader:
+        v_feats = [f.to(dev, non_blocking=True) for f in v_feats]
+        v_masks = [m.to(dev, non_blocking=True) for m in v_masks] if v_masks is not None else None
+        if beam_size is None:
+            ys = model.greedy_decode_ids(v_feats, v_masks, max_len=max_len)
+        else:
+            ys = model.beam_decode_ids(v_feats, v_masks, beam_size=beam_size, max_len=max_len)
+        caps = None
+        if level == "word" or return_captions:
+            caps = [_strip_special(c) for c in model._ids_to_captions(ys)]
+            vid2result.update(zip(vids, caps))
+        # a by_video loader walks the feature directory: clips the split holds no reference entry for are decoded, not scored
+        known = [i for i, v in enumerate(vids) if v in scorer.vid_row]
+        if not known:
+            continue
+        if level == "token":
+            rows = ys if len(known) == len(vids) else ys.index_select(0, torch.tensor(known, device=ys.device))
+        else:
+            rows = _word_rows(scorer, [caps[i] for i in known], dev)
+        scorer.add(rows, [vids[i] for i in known])
+    out = scorer.result()
+    return (out, vid2result) if return_captions else out
+
+
+def metric_earlystop_score(metrics: dict) -> float:
+    """The number metric early stopping watches (train.py:262-270: EarlyStopping(-sum of the metrics, ...)): metrics["sum"] =
+    Bleu_4 + ROUGE_L + CIDEr.  Three terms where the reference's sum has four: METEOR is not computed here, so the values are not
+    comparable with the reference's, only with each other."""
+    return float(metrics["sum"])
 
 
 def make_coco_sample(prediction_dict: Dict[str, str], ground_truth_dict: Dict[str, List[str]]):

@@ -700,6 +700,109 @@ def scst_advantages(rewards, baseline=None, adv=None, base_out=None, means=None)
     return adv, base_out, means
 
 
+def check_capmetric_ids(ids, device=None):
+    """The refusals of the caption-metric kernels' candidate table, before any launch: int64 [C, L] on the GPU (on `device` when
+    given), 1 <= L <= 1 + VCT_CIDER_MAX_LEN columns (column 0 is the start token)."""
+    if not torch.is_tensor(ids) or ids.dtype != torch.int64 or ids.dim() != 2:
+        raise ValueError(f"capmetric: ids must be an int64 tensor [C, L], got {getattr(ids, 'dtype', type(ids))} {tuple(getattr(ids, 'shape', ()))}")
+    if not ids.is_cuda or (device is not None and ids.device != device):
+        raise ValueError(f"capmetric: ids must live on the metric tables' device, got {ids.device}")
+    Cn, Lc = ids.shape
+    if Cn < 1 or Lc < 1 or Lc > 1 + L.CIDER_MAX_LEN:
+        raise ValueError(f"capmetric: ids [C >= 1, 1 <= L <= {1 + L.CIDER_MAX_LEN}] (start column + at most {L.CIDER_MAX_LEN} tokens), "
+                         f"got {tuple(ids.shape)}")
+
+
+def _capmetric_out(x, shape, dtype, dev, what):
+    if x is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if x.dtype != dtype or tuple(x.shape) != tuple(shape) or not x.is_contiguous() or x.device != dev:
+        raise ValueError(f"{what} must be contiguous {dtype} {list(shape)} on {dev}, got {x.dtype} {tuple(x.shape)} on {x.device}")
+    return x
+
+
+def _capmetric_rows(ids, vid_rows, what):
+    Cn = ids.shape[0]
+    if (not torch.is_tensor(vid_rows) or vid_rows.dtype != torch.int32 or tuple(vid_rows.shape) != (Cn,) or not vid_rows.is_contiguous()
+            or vid_rows.device != ids.device):
+        raise ValueError(f"{what}: vid_rows must be contiguous int32 [C = {Cn}] on {ids.device}, got "
+                         f"{getattr(vid_rows, 'dtype', type(vid_rows))} {tuple(getattr(vid_rows, 'shape', ()))}")
+
+
+def capmetric_counts(ids, vid_rows, tab, counts=None, rouge=None):
+    """Per-caption BLEU / ROUGE-L statistics on the device (include/vct_hip.h, vct_capmetric_counts).  ids: int64 [C, L] (any
+    strides, column 0 the start token); vid_rows: int32 [C] table rows; tab: metrics.DeviceCaptionMetrics (its device tensors `t`,
+    end_id, beta_sq, n_videos); counts int32 [C, 12] / rouge fp64 [C, 3]: contiguous or None (allocated).  Returns (counts, rouge).
+    Enqueued on the current stream; no host synchronisation."""
+    check_capmetric_ids(ids)
+    _capmetric_rows(ids, vid_rows, "capmetric_counts")
+    Cn, Lc = ids.shape
+    t = tab.t
+    if t["ref_tok"].device != ids.device:
+        raise ValueError(f"capmetric_counts: the metric tables live on {t['ref_tok'].device}, ids on {ids.device}")
+    if not float(tab.beta_sq) > 0.0:
+        raise ValueError(f"capmetric_counts: beta_sq > 0, got {tab.beta_sq}")
+    counts = _capmetric_out(counts, (Cn, L.CAPMETRIC_COUNT_COLS), torch.int32, ids.device, "capmetric_counts: counts")
+    rouge = _capmetric_out(rouge, (Cn, 3), torch.float64, ids.device, "capmetric_counts: rouge")
+    d = L.CapMetricDesc()
+    d.C, d.L = Cn, Lc - 1
+    d.ids, d.stride_c, d.stride_l = ids.data_ptr(), ids.stride(0), ids.stride(1)
+    d.end_id, d.vid_rows, d.n_videos, d.beta_sq = int(tab.end_id), vid_rows.data_ptr(), int(tab.n_videos), float(tab.beta_sq)
+    for k in ("vid_ref_ptr", "ref_tok_ptr", "ref_tok"):
+        setattr(d, k, t[k].data_ptr())
+    d.counts, d.rouge = counts.data_ptr(), rouge.data_ptr()
+    L.check(L.load().vct_capmetric_counts(d, L.stream_ptr()), "vct_capmetric_counts")
+    return counts, rouge
+
+
+def cider_d_eval(ids, vid_rows, tab, out=None):
+    """The evaluation CIDEr of decoded ids on the device (include/vct_hip.h, vct_cider_d_eval): ops.cider_d's score with the end
+    token dropped, un-rounded.  ids: int64 [C, L] (any strides); vid_rows: int32 [C]; tab: as ops.cider_d's (device tensors `t`
+    and the scalars n, end_id, log_nvid, two_sigma_sq, n_videos, table_cap); out: fp64 [C] contiguous or None.  Returns out."""
+    check_capmetric_ids(ids)
+    _capmetric_rows(ids, vid_rows, "cider_d_eval")
+    Cn, Lc = ids.shape
+    if not 1 <= int(tab.n) <= L.CIDER_MAX_ORDER:
+        raise ValueError(f"cider_d_eval: n-gram orders 1 .. {L.CIDER_MAX_ORDER}, got n = {tab.n}")
+    t = tab.t
+    if t["table_keys"].device != ids.device:
+        raise ValueError(f"cider_d_eval: the metric tables live on {t['table_keys'].device}, ids on {ids.device}")
+    out = _capmetric_out(out, (Cn,), torch.float64, ids.device, "cider_d_eval: out")
+    d = L.CiderDesc()
+    d.B, d.N, d.L, d.n = Cn, 1, Lc - 1, int(tab.n)
+    d.ids = ids.data_ptr()
+    d.stride_b, d.stride_n, d.stride_l = ids.stride(0), 0, ids.stride(1)
+    d.end_id, d.log_nvid, d.two_sigma_sq = int(tab.end_id), float(tab.log_nvid), float(tab.two_sigma_sq)
+    d.vid_rows, d.n_videos, d.table_cap = vid_rows.data_ptr(), int(tab.n_videos), int(tab.table_cap)
+    for k in ("table_keys", "table_idf", "vid_ref_ptr", "ref_len", "ref_norm", "ref_ent_ptr", "ent_keys", "ent_w"):
+        setattr(d, k, t[k].data_ptr())
+    d.reward = None
+    L.check(L.load().vct_cider_d_eval(d, out.data_ptr(), L.stream_ptr()), "vct_cider_d_eval")
+    return out
+
+
+def capmetric_finish(counts, rouge, cider=None, out=None):
+    """The corpus-level fold of the per-caption rows (include/vct_hip.h, vct_capmetric_finish).  counts int32 [C, 12], rouge fp64
+    [C, 3], cider fp64 [C] or None; all contiguous on one GPU.  Returns out fp64 [8] = {Bleu_1..4, ROUGE_L, CIDEr, their sum with
+    Bleu_4, C}.  Enqueued on the current stream; no host synchronisation."""
+    if (not torch.is_tensor(counts) or counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[1] != L.CAPMETRIC_COUNT_COLS
+            or not counts.is_cuda or not counts.is_contiguous() or counts.shape[0] < 1):
+        raise ValueError(f"capmetric_finish: counts must be contiguous int32 [C >= 1, {L.CAPMETRIC_COUNT_COLS}] on the GPU, got "
+                         f"{getattr(counts, 'dtype', type(counts))} {tuple(getattr(counts, 'shape', ()))}")
+    Cn = counts.shape[0]
+    if not torch.is_tensor(rouge):
+        raise ValueError("capmetric_finish: rouge must be a tensor")
+    _capmetric_out(rouge, (Cn, 3), torch.float64, counts.device, "capmetric_finish: rouge")
+    if cider is not None:
+        if not torch.is_tensor(cider):
+            raise ValueError("capmetric_finish: cider must be a tensor or None")
+        _capmetric_out(cider, (Cn,), torch.float64, counts.device, "capmetric_finish: cider")
+    out = _capmetric_out(out, (8,), torch.float64, counts.device, "capmetric_finish: out")
+    L.check(L.load().vct_capmetric_finish(Cn, counts.data_ptr(), rouge.data_ptr(), L.ptr(cider), out.data_ptr(), L.stream_ptr()),
+            "vct_capmetric_finish")
+    return out
+
+
 def match_loss_workspace_bytes(B: int, Dt: int) -> int:
     """Bytes of caller-owned workspace ops.match_loss needs (include/vct_hip.h); raises for a shape the kernels do not take."""
     n = int(L.load().vct_match_loss_workspace_bytes(int(B), int(Dt)))
