@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VCT_ABI_VERSION 15
+#define VCT_ABI_VERSION 16
 
 enum { VCT_F32 = 0, VCT_BF16 = 1 };
 enum { VCT_ACT_NONE = 0, VCT_ACT_GELU = 1, VCT_ACT_RELU = 2 };
@@ -91,9 +91,15 @@ typedef struct vct_gemm_desc {
   const uint32_t* seed; uint32_t site; float p_drop; /* dropout on C (after act / inside dact) */
   float* bias_grad;                         /* optional [M] fp32: sum over K of op(A) (db for ta=1) */
   void* workspace; int64_t workspace_bytes; /* split-K partials (fp32); NULL = never split */
-  int32_t split_k;                          /* 0 auto, 1 none, >1 forced */
+  int32_t split_k;                          /* 0 auto, 1 none, >1 forced.  A forced split that cannot be honoured is REFUSED with
+                                               VCT_E_WORKSPACE, never quietly dropped: no / too small a workspace, or a product with
+                                               an epilogue (bias, act, preact, addend, dact_src, dropout, adam) that cannot reduce
+                                               inside the kernel -- no tile_counters, fp32 operands, or more than 16 MB of fp32
+                                               partials (split * M * N * 4).  The automatic split (0) falls back to no split there;
+                                               a plain product falls back to the two-pass reduce. */
   int32_t reserved;                         /* 0; kernel-selection override for tests / A-B probes: 1-9 (+10 x buffers) = a tile of
-                                               the general kernel, 100 = force / 99 = forbid the persistent-tile layer kernel */
+                                               the general kernel, 100 = force / 99 = forbid the persistent-tile layer kernel;
+                                               vct_gemm_last_route (below) reports the kernel that was actually launched */
   int32_t n_tile_counters;                  /* ints available at tile_counters */
   int32_t* tile_counters;                   /* optional, see below */
   const vct_gemm_adam* adam;                /* optional (NULL = none): optimizer epilogue of the dW form, see vct_gemm_adam */
@@ -105,6 +111,22 @@ typedef struct vct_gemm_desc {
  * + 1 is always enough); without (NULL / too few) the two-pass reduce is used.  GEMMs that may run CONCURRENTLY
  * (different streams) must not share counters or workspace. */
 int vct_gemm(const vct_gemm_desc* d, void* stream);
+/* The route the calling thread's last vct_gemm / vct_gemm_grouped took: which kernel was launched, with which tile and split.  A
+ * host-side, thread-local record written where the launch is issued (read-only here; all zero before the first GEMM of the thread;
+ * a call that returned an error leaves it unspecified).  Tests assert it, so that a case written for one kernel cannot fall through
+ * to another unnoticed when an eligibility threshold moves (`reserved` above forces a route, this reports the one taken).
+ * out[0 .. VCT_GEMM_ROUTE_INTS):
+ *   [0] kernel: 1 general bf16, 2 general fp32, 3 skinny, 4 persistent 256 x 256 (round-5 kernel), 5 persistent 256 x 256
+ *       (pipelined g32 kernel), 6 persistent-tile layer kernel, 7 grouped
+ *   [1] bm  [2] bn  (tile; skinny: 16 x 16 ntl)   [3] nbuf (operand stages; 0: no LDS staging)
+ *   [4] variant: the general / grouped kernel's eight-wave variant id (0 four waves, 1 128x128, 4 128x64, 6 256x128, 7 320x128,
+ *       9 64x128); skinny: ntl; layer kernel: 1 = the epilogue instantiation, 0 = the plain one
+ *   [5] split (grouped: the largest of the problems)   [6] 1 = the split was reduced inside the producing kernel (tile counters)
+ *   [7] 1 = a separate reduce launch followed
+ *   [8] grouped: number of problems   [9 .. 9 + VCT_GEMM_GROUP_MAX) grouped: each problem's split
+ * Returns VCT_E_ARG when out is NULL or n < VCT_GEMM_ROUTE_INTS. */
+#define VCT_GEMM_ROUTE_INTS 17
+int vct_gemm_last_route(int32_t* out, int32_t n);
 /* bytes of workspace vct_gemm may use for this descriptor (0 if it will not split) */
 int64_t vct_gemm_workspace_bytes(const vct_gemm_desc* d);
 

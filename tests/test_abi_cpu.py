@@ -38,7 +38,7 @@ def test_binding_covers_header(lib_path):
     from vct_amd import _lib
     assert sorted(set(declared_symbols())) == sorted(set(_lib.exported_symbols()))
     lib = _lib.load()
-    assert lib.vct_abi_version() == _lib.ABI_VERSION == 15
+    assert lib.vct_abi_version() == _lib.ABI_VERSION == 16
     buf = ctypes.create_string_buffer(128)
     assert lib.vct_build_info(buf, 128) > 0 and b"gfx950" in buf.value
 
@@ -57,6 +57,30 @@ def test_argument_errors_are_codes_not_crashes(lib_path):
         _lib.check(-2, "x")
     with pytest.raises(RuntimeError):
         _lib.check(700, "x")
+
+
+def test_gemm_last_route_is_zero_before_any_gemm(lib_path):
+    """vct_gemm_last_route: a host-side record; all zero before this thread ran a GEMM (a refused descriptor records nothing), and a
+    buffer shorter than the record is refused."""
+    import threading
+    from vct_amd import _lib
+    lib = _lib.load()
+    n = _lib.GEMM_ROUTE_INTS
+    assert n == 17
+    got = {}
+
+    def fresh_thread():                                    # the record is thread-local: a new thread has run no GEMM whatever ran before
+        buf = (ctypes.c_int32 * n)(*([7] * n))
+        assert lib.vct_gemm(_lib.GemmDesc(), None) == -1   # refused before any launch
+        got["rc"] = lib.vct_gemm_last_route(buf, n)
+        got["rec"] = list(buf)
+        short = (ctypes.c_int32 * n)(*([7] * n))
+        got["short"] = (lib.vct_gemm_last_route(short, n - 1), list(short))
+        got["null"] = lib.vct_gemm_last_route(None, n)
+    t = threading.Thread(target=fresh_thread)
+    t.start(); t.join()
+    assert got["rc"] == 0 and got["rec"] == [0] * n
+    assert got["short"] == (-1, [7] * n) and got["null"] == -1
 
 
 def test_new_entry_points_validate_arguments(lib_path):

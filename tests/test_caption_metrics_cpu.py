@@ -249,6 +249,6 @@ def test_descriptor_matches_the_c_header(tmp_path):
     exe = tmp_path / "sz"
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
     got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == [ctypes.sizeof(_lib.CapMetricDesc), _lib.CAPMETRIC_COUNT_COLS, 15] + [getattr(_lib.CapMetricDesc, f).offset for f in fields]
+    assert got == [ctypes.sizeof(_lib.CapMetricDesc), _lib.CAPMETRIC_COUNT_COLS, 16] + [getattr(_lib.CapMetricDesc, f).offset for f in fields]
     assert metrics.COUNT_COLS == _lib.CAPMETRIC_COUNT_COLS
-    assert {"vct_capmetric_counts", "vct_cider_d_eval", "vct_capmetric_finish"} <= set(_lib.exported_symbols()) and _lib.ABI_VERSION == 15
+    assert {"vct_capmetric_counts", "vct_cider_d_eval", "vct_capmetric_finish"} <= set(_lib.exported_symbols()) and _lib.ABI_VERSION == 16

@@ -185,4 +185,4 @@ def test_cider_descriptor_matches_the_c_header(tmp_path):
 
 def test_binding_lists_the_new_entries():
     from vct_amd import _lib
-    assert {"vct_cider_d", "vct_scst_advantages"} <= set(_lib.exported_symbols()) and _lib.ABI_VERSION == 15
+    assert {"vct_cider_d", "vct_scst_advantages"} <= set(_lib.exported_symbols()) and _lib.ABI_VERSION == 16

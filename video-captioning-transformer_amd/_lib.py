@@ -10,8 +10,9 @@ LIB_PATH = os.path.join(_PKG, "libvct_hip.so")
 _AB_LIB = os.environ.get("VCT_LIB_PATH")      # developer A/B: load another build of the SAME ABI (tools/ab_build.sh)
 
 F32, BF16 = 0, 1
-ABI_VERSION = 15
+ABI_VERSION = 16
 GEMM_GROUP_MAX = 8
+GEMM_ROUTE_INTS = 17
 ACT = {"none": 0, None: 0, "gelu": 1, "relu": 2}
 _ERR = {-1: "VCT_E_ARG (null pointer / bad enum)", -2: "VCT_E_SHAPE (unsupported shape)",
         -3: "VCT_E_ALIGN (leading dimension / alignment)", -4: "VCT_E_WORKSPACE (workspace too small)"}
@@ -208,6 +209,7 @@ _SIGS = {
     "vct_abi_version": (C.c_int, []),
     "vct_build_info": (C.c_int, [C.c_char_p, C.c_int]),
     "vct_gemm": (C.c_int, [C.POINTER(GemmDesc), vp]),
+    "vct_gemm_last_route": (C.c_int, [C.POINTER(i32), i32]),
     "vct_gemm_workspace_bytes": (i64, [C.POINTER(GemmDesc)]),
     "vct_gemm_grouped": (C.c_int, [C.POINTER(GemmDesc), i32, vp]),
     "vct_gemm_grouped_workspace_bytes": (i64, [C.POINTER(GemmDesc), i32, i32]),

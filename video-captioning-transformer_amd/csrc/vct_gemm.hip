@@ -294,6 +294,14 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ partial, TO* __re
 
 struct Plan { int bm, bn, nbuf, waves8; int split; int tiles_m, tiles_n, nkt, kt_per; };
 
+// the route of this thread's last GEMM call (vct_gemm_last_route): a handful of host stores per call
+static thread_local int32_t g_route[VCT_GEMM_ROUTE_INTS];
+void gemm_route_set(int kernel, int bm, int bn, int nbuf, int variant, int split, int in_kernel_reduce, int reduce_launch) {
+  memset(g_route, 0, sizeof(g_route));
+  g_route[0] = kernel; g_route[1] = bm; g_route[2] = bn; g_route[3] = nbuf; g_route[4] = variant;
+  g_route[5] = split; g_route[6] = in_kernel_reduce; g_route[7] = reduce_launch;
+}
+
 static bool gemm_can_split(const vct_gemm_desc* d) {
   return d->bias == nullptr && d->act == VCT_ACT_NONE && d->preact == nullptr &&
          d->addend == nullptr && d->dact_src == nullptr && !(d->seed != nullptr && d->p_drop > 0.0f);
@@ -495,6 +503,12 @@ static void fill_params(const vct_gemm_desc* d, const Plan& pl, GemmP& p) {
   }
 }
 
+extern "C" int vct_gemm_last_route(int32_t* out, int32_t n) {
+  if (out == nullptr || n < VCT_GEMM_ROUTE_INTS) return VCT_E_ARG;
+  memcpy(out, g_route, sizeof(g_route));
+  return VCT_OK;
+}
+
 extern "C" int vct_gemm(const vct_gemm_desc* d, void* stream) {
   const int ok = check_desc(d);
   if (ok != VCT_OK) return ok;
@@ -536,6 +550,8 @@ extern "C" int vct_gemm(const vct_gemm_desc* d, void* stream) {
   GemmP p;
   fill_params(d, pl, p);
   const dim3 grid(pl.tiles_m * pl.tiles_n, 1, pl.split);
+  gemm_route_set(d->dtype == VCT_BF16 ? 1 : 2, pl.bm, pl.bn, d->dtype == VCT_BF16 ? (pl.nbuf == 1 ? 1 : 2) : 1, pl.waves8, pl.split,   // (stages as instantiated: launch_nbuf)
+                 pl.split > 1 && p.counters != nullptr, pl.split > 1 && p.counters == nullptr);
   int rc;
   if (d->dtype == VCT_BF16) {
     rc = gemm_bf16_v2_dispatch(d, p, pl.bm, pl.bn, pl.nbuf, grid, st);
@@ -623,6 +639,8 @@ extern "C" int vct_gemm_grouped(const vct_gemm_desc* descs, int32_t n, void* str
   GemmGroupP g;
   g.n = n;
   int wg = 0;
+  gemm_route_set(7, t.bm, t.bn, 2, t.waves8, 1, 0, 0);
+  g_route[8] = n;
   // group-level XCD map (vct_gemm_bf16_kernel.h, gemm_bf16_v2_grouped_kernel) whenever no problem is split; VCT_GROUP_MAP=0: A/B
   static const bool group_map_on = [] { const char* e = getenv("VCT_GROUP_MAP"); return !(e && e[0] == '0'); }();
   bool group_map = group_map_on;
@@ -635,6 +653,9 @@ extern "C" int vct_gemm_grouped(const vct_gemm_desc* descs, int32_t n, void* str
       if (d->workspace == nullptr || d->workspace_bytes < ws_bytes(d, pl)) return VCT_E_WORKSPACE;
     }
     fill_params(d, pl, g.p[i]);
+    g_route[9 + i] = pl.split;
+    if (pl.split > g_route[5]) g_route[5] = pl.split;
+    if (pl.split > 1) g_route[6] = 1;
     g.start[i] = wg;
     wg += group_map ? pl.tiles_m * pl.tiles_n : (pl.tiles_m * pl.tiles_n * pl.split + 7) & ~7;
   }

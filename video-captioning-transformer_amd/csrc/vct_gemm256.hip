@@ -300,10 +300,15 @@ static bool g32_takes(int form_bit) {
 
 template <int TA, int TB, typename TO> static int g256_launch(const G256P& p, hipStream_t st) {
   constexpr int form_bit = (TA == 1) ? 4 : (TB == 0 ? 2 : (sizeof(TO) == 4 ? 8 : 1));
-  if (g32_takes(form_bit) && p.dbg == 0 && g32_eligible(p, TA == 1, TB == 0)) return g32_launch<TA, TB, TO, 0>(p, st);
+  const int reduce = p.partial != nullptr && p.split > 1;      // the caller's reduce launch over the fp32 partials
+  if (g32_takes(form_bit) && p.dbg == 0 && g32_eligible(p, TA == 1, TB == 0)) {
+    gemm_route_set(5, G256_BM, G256_BN, 2, 0, p.split, 0, reduce);
+    return g32_launch<TA, TB, TO, 0>(p, st);
+  }
   if (p.adam.param != nullptr) return VCT_E_ARG;             // (gemm256_try never gets here: the round-5 kernel has no optimizer epilogue)
   static vct::DynLdsOptIn optin;
   if (hipError_t e = optin.ensure((const void*)gemm256_kernel<TA, TB, TO>, G256_LDS); e != hipSuccess) return (int)e;
+  gemm_route_set(4, G256_BM, G256_BN, 2, 0, p.split, 0, reduce);
   vct::launch(gemm256_kernel<TA, TB, TO>, dim3(persistent_grid(st)), dim3(512), (size_t)G256_LDS, st, p);
   VCT_CHECK_LAUNCH();
   return VCT_OK;

@@ -49,4 +49,8 @@ struct GemmGroupP {
   GemmP p[VCT_GEMM_GROUP_MAX];
 };
 
+// Host-side record of the route the last vct_gemm / vct_gemm_grouped of this thread took (include/vct_hip.h,
+// vct_gemm_last_route): written where the launch is issued, read by tests.  Defined in vct_gemm.hip.
+void gemm_route_set(int kernel, int bm, int bn, int nbuf, int variant, int split, int in_kernel_reduce, int reduce_launch);
+
 }  // namespace vct

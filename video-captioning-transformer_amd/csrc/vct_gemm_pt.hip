@@ -353,6 +353,7 @@ int gemm_pt_try(const vct_gemm_desc* d, hipStream_t st, bool* used) {
   const int bm = tile == 0 ? 128 : 64;
   p.tiles_m = (d->M + bm - 1) / bm; p.tiles_n = (d->N + 127) / 128;
   const bool epi = d->act != VCT_ACT_NONE || d->preact || d->addend || d->dact_src || (d->seed && d->p_drop > 0.0f);
+  gemm_route_set(6, bm, 128, 2, epi ? 1 : 0, 1, 0, 0);
   const int rc = form == 1 ? gpt_dispatch<0, 1>(p, tile, epi, st) : gpt_dispatch<0, 0>(p, tile, epi, st);
   if (rc == VCT_OK) *used = true;
   return rc;

@@ -216,6 +216,10 @@ int gemm_skinny_try(const vct_gemm_desc* d, hipStream_t st, bool* used) {
   p.act = d->act; p.bias = d->bias; p.addend = d->addend; p.ld_addend = d->ld_addend;
   p.add_f32 = 0;
   p.xpre = nullptr; p.ld_pre = 0; p.ln_g = p.ln_b = nullptr; p.xnorm = nullptr; p.ld_norm = 0; p.ids = nullptr; p.id_stride = 0;
+  {
+    const int ntl = skinny_ntl(p.M, p.N);
+    gemm_route_set(3, 16, 16 * ntl, 0, ntl, 1, 0, 0);
+  }
   if (d->out_dtype == VCT_BF16) skinny_launch<bf16_t, false, 4>(p, st);
   else skinny_launch<float, false, 4>(p, st);
   VCT_CHECK_LAUNCH();

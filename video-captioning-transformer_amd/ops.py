@@ -128,6 +128,20 @@ def gemm_grouped(items, scratch: GemmScratch, split_k: int = 0, tile: int = 0):
     L.check(lib.vct_gemm_grouped(arr, n, L.stream_ptr()), "vct_gemm_grouped")
 
 
+_ROUTE_KERNELS = {0: None, 1: "general_bf16", 2: "general_f32", 3: "skinny", 4: "g256", 5: "g256_g32", 6: "layer_pt", 7: "grouped"}
+
+
+def gemm_last_route() -> dict:
+    """The route this thread's last gemm / gemm_grouped took (include/vct_hip.h, vct_gemm_last_route): kernel id and name, tile,
+    operand stages, variant id, split, where the split was reduced; for a grouped launch also each problem's split."""
+    lib = L.load()
+    buf = (L.i32 * L.GEMM_ROUTE_INTS)()
+    L.check(lib.vct_gemm_last_route(buf, L.GEMM_ROUTE_INTS), "vct_gemm_last_route")
+    r = list(buf)
+    return {"kernel": r[0], "name": _ROUTE_KERNELS.get(r[0]), "bm": r[1], "bn": r[2], "nbuf": r[3], "variant": r[4], "split": r[5],
+            "in_kernel_reduce": bool(r[6]), "reduce_launch": bool(r[7]), "group_splits": r[9:9 + r[8]]}
+
+
 def gemm_workspace_bytes(M: int, N: int, K: int, dtype: torch.dtype) -> int:
     """Upper bound of the split-K workspace the weight-gradient GEMM [M,N] (reduction K) may use."""
     lib = L.load()
