@@ -700,6 +700,50 @@ int vct_scale(float* x, int64_t n, float s, void* stream);
 int vct_axpby(float* out, const float* x, float a, const float* y, float b, int64_t n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Text-video retrieval evaluation of the matching head (csrc/vct_retrieval.hip), fp32 end to end: the ranks of text->video and
+ * video->text retrieval over a whole split and their statistics, without ever storing the [Nt, Nv] score matrix.
+ *   text [Nt, Dt], vid [Nv, Dt] with leading dimensions; gt int32 [Nt]: the video row each text belongs to (any number of texts per
+ *   video, in any order, possibly none).  s[i, j] = t^_i . v^_j as in vct_match_loss (rows L2-normalised, no epsilon).
+ *   VCT_RETRIEVAL_PLAIN:         f = s (CSL's exp(temp) factor is monotone and dropped)
+ *   VCT_RETRIEVAL_DUAL_SOFTMAX:  f[i, j] = s[i, j] * softmax_i(s[:, j] / *tau)[i] (what CSL_WDS trains, without its factor B);
+ *                                tau: DEVICE scalar, non-NULL exactly in this mode.
+ * Ranks are 1-based, ties go to the lower index (a stable descending sort):
+ *   ranks_t2v[i] = 1 + #{ j : f[i,j] > f[i,g] or (f[i,j] == f[i,g] and j < g) },  g = gt[i]
+ *   ranks_v2t[j] = 1 + #{ i : f[i,j] > f[i*,j] or (f[i,j] == f[i*,j] and i < i*) },  i* the best-scoring own text of video j (the
+ *                  lowest index on ties): the best-ranked-own-caption convention of multi-sentence retrieval.
+ * A video without a text, and a text whose gt is outside [0, Nv) (never used as an index), get rank 0 and enter no statistic; such
+ * a text still competes in video->text and takes part in the column softmax.
+ * out[12]: per direction (text->video, then video->text) {R@1, R@5, R@10 as fractions, median rank (numpy's: the mean of the two
+ * middle ranks of an even count), mean rank, number of queries counted}; all zero for a direction without a query.
+ * f[i, j] has the same bits wherever it is computed (one fixed summation order over Dt, the inverse norms computed once), so the
+ * comparisons above compare like with like at any tile position and for any Nt / Nv.  Integer atomics only; the column
+ * statistics of the dual softmax are per-tile partials folded in tile order: two calls on the same inputs agree bitwise.
+ * Plain: one sweep over the matrix; dual softmax: one more before it for the column statistics.  phases: 0 = everything; else a
+ * bit set of VCT_RETRIEVAL_PH_* to run (timing one phase; a phase reads what the earlier ones left in the workspace and outputs).
+ * Dt a multiple of 4 up to 1024, 1 <= Nt, Nv <= 2^20, ld >= Dt (VCT_E_SHAPE); ld a multiple of 4, text / vid / workspace 16-byte,
+ * out 8-byte, the int32 arrays 4-byte aligned (VCT_E_ALIGN); NULL operand, bad mode / phases, tau missing or unexpected (VCT_E_ARG);
+ * workspace: vct_retrieval_workspace_bytes(Nt, Nv, Dt, mode) bytes (0 for an unsupported shape or mode), owned by the caller
+ * (VCT_E_WORKSPACE).  No allocation, no synchronisation, no host read.
+ * --------------------------------------------------------------------------------------------- */
+enum { VCT_RETRIEVAL_PLAIN = 0, VCT_RETRIEVAL_DUAL_SOFTMAX = 1 };
+enum { VCT_RETRIEVAL_PH_PREP = 1, VCT_RETRIEVAL_PH_STATS = 2, VCT_RETRIEVAL_PH_GT = 4, VCT_RETRIEVAL_PH_COUNT = 8,
+       VCT_RETRIEVAL_PH_FINISH = 16 };
+typedef struct vct_retrieval_desc {
+  int32_t Nt, Nv, Dt, mode;
+  const float* text; int64_t ld_text;
+  const float* vid; int64_t ld_vid;
+  const int32_t* gt;             /* [Nt] */
+  const float* tau;
+  int32_t* ranks_t2v;            /* [Nt] */
+  int32_t* ranks_v2t;            /* [Nv] */
+  double* out;                   /* [12] */
+  void* workspace; int64_t workspace_bytes;
+  int32_t phases, reserved;
+} vct_retrieval_desc;
+int vct_retrieval_ranks(const vct_retrieval_desc* d, void* stream);
+int64_t vct_retrieval_workspace_bytes(int Nt, int Nv, int Dt, int mode);
+
+/* ---------------------------------------------------------------------------------------------
  * Batch assembly from a DEVICE-RESIDENT feature store (a split's clips packed into store [rows, E] fp32, clip i =
  * rows offsets[i] .. offsets[i+1]): out[b, t, :] = store[offsets[idx[b]] + t] for t < len(clip idx[b]), else 0;
  * mask[b, t] = 1 where padded.  out: [B, Tmax, E] of out_dtype (fp32, or bf16 = the encoder's compute type, which

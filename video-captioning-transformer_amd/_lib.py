@@ -170,6 +170,17 @@ class MatchAggDesc(C.Structure):
                 ("dagg", vp), ("dmem", vp)]
 
 
+RETRIEVAL_MODE = {"plain": 0, "dual_softmax": 1}
+RETRIEVAL_PHASE = {"prep": 1, "stats": 2, "gt": 4, "count": 8, "finish": 16}
+
+
+class RetrievalDesc(C.Structure):
+    """include/vct_hip.h, vct_retrieval_desc: text->video / video->text ranks and their statistics over a whole split."""
+    _fields_ = [("Nt", i32), ("Nv", i32), ("Dt", i32), ("mode", i32), ("text", vp), ("ld_text", i64), ("vid", vp), ("ld_vid", i64),
+                ("gt", vp), ("tau", vp), ("ranks_t2v", vp), ("ranks_v2t", vp), ("out", vp), ("workspace", vp), ("workspace_bytes", i64),
+                ("phases", i32), ("reserved", i32)]
+
+
 class SampleCtl(C.Structure):
     """include/vct_hip.h, vct_sample_ctl: the settings vct_sample_select reads from device memory."""
     _fields_ = [("seed", u32), ("top_k", i32), ("inv_temp", f32), ("top_p", f32)]
@@ -240,6 +251,8 @@ _SIGS = {
     "vct_match_loss_workspace_bytes": (i64, [C.c_int, C.c_int]),
     "vct_match_agg_fwd": (C.c_int, [C.POINTER(MatchAggDesc), vp]),
     "vct_match_agg_bwd": (C.c_int, [C.POINTER(MatchAggDesc), vp]),
+    "vct_retrieval_ranks": (C.c_int, [C.POINTER(RetrievalDesc), vp]),
+    "vct_retrieval_workspace_bytes": (i64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "vct_scale": (C.c_int, [vp, i64, f32, vp]),
     "vct_axpby": (C.c_int, [vp, vp, f32, vp, f32, i64, vp]),
     "vct_embed_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, vp, vp, vp, u32, f32, vp]),

@@ -233,6 +233,65 @@ def metric_earlystop_score(metrics: dict) -> float:
     return float(metrics["sum"])
 
 
+@torch.no_grad()
+def eval_retrieval(model, dataloader, text_feats_fn=None, mode: Optional[str] = None, tau=None) -> dict:
+    """Text-video retrieval over the split a by_video loader walks (retrieval.py): embeds every batch's videos
+    (MMT4Caption.embed_videos), takes the text features of EVERY reference caption of those videos (dataset.video2caption;
+    text_feats_fn(captions, vids) -> fp32 [len(captions), text_encoder.dim] as in val_epoch, vids[k] the video of caption k, or the
+    installed text_encoder.backend) and scores recall at 1 / 5 / 10, median and mean rank in both directions on the device.
+    mode None: 'dual_softmax' with the head's temperature for a CSL_WDS head, 'plain' otherwise; tau overrides the temperature.
+    A video without a reference entry is embedded and competes, but is no video->text query.  One device->host sync.
+    Returns {"t2v": {R1, R5, R10, MedianR, MeanR, n}, "v2t": {...}, "rsum"}; recalls in percent."""
+    from .retrieval import DeviceRetrievalMetrics
+    model.check_task("match")
+    dataset = getattr(dataloader, "dataset", None) or getattr(dataloader, "ds", None)
+    v2c = getattr(dataset, "video2caption", None)
+    if v2c is None:
+        raise ValueError("eval_retrieval: the loader's dataset has no video2caption to take the reference captions from")
+    if mode is None:
+        mode = "dual_softmax" if model.matching.loss_fn.kind == "CSL_WDS" else "plain"
+    if mode == "dual_softmax" and tau is None:
+        tau = model.matching.loss_fn.temperature
+        if tau is None:
+            raise ValueError("eval_retrieval: mode 'dual_softmax' needs a tau: the head has no temperature, pass tau=")
+        tau = tau.detach()
+    model.eval()
+    dev = model.device
+    batches = []
+    n_videos = n_texts = 0
+    scorer = DeviceRetrievalMetrics(mode, tau, dev)
+    # the scorer's matrices are sized once: embed first (device tensors, nothing is read back), then copy the rows in
+    for v_feats, v_masks, _caps, vids in dataloader:
+        v_feats = [f.to(dev, non_blocking=True) for f in v_feats]
+        v_masks = [m.to(dev, non_blocking=True) for m in v_masks] if v_masks is not None else None
+        emb = model.embed_videos(v_feats, v_masks)
+        caps, cap_vids = [], []
+        for v in vids:
+            for c in v2c.get(v, ()):
+                caps.append(c)
+                cap_vids.append(v)
+        text = None
+        if caps:
+            text = text_feats_fn(caps, cap_vids) if text_feats_fn is not None else model.text_encoder(caps)
+            text = text.to(dev, non_blocking=True)
+        batches.append((emb, list(vids), text, cap_vids))
+        n_videos += len(vids)
+        n_texts += len(caps)
+    if not n_videos or not n_texts:
+        raise ValueError(f"eval_retrieval: {n_videos} videos and {n_texts} reference captions: nothing to rank")
+    scorer.begin(n_videos, n_texts)
+    for emb, vids, text, cap_vids in batches:
+        scorer.add_videos(emb, vids)
+        if text is not None:
+            scorer.add_texts(text, cap_vids)
+    return scorer.result()
+
+
+def retrieval_earlystop_score(metrics: dict) -> float:
+    """The number retrieval early stopping watches: metrics["rsum"], the sum of the six recalls (use it as metric_earlystop_score)."""
+    return float(metrics["rsum"])
+
+
 def make_coco_sample(prediction_dict: Dict[str, str], ground_truth_dict: Dict[str, List[str]]):
     """eval.py:24-39: (gts, samples, IDs) in the layout COCOScorer.score expects."""
     samples, IDs, gts = {}, [], {}

@@ -494,6 +494,26 @@ class MMT4Caption(nn.Module):
             return self._match_forward_kernels(feats, mask, text, self.training, backward=False)["loss"][0].clone()
         return _MatchFn.apply(self, feats, mask, text, *[self._ps.params[n] for n in self._ps.names]).reshape(())
 
+    @torch.no_grad()
+    def embed_videos(self, video_feats, video_masks) -> torch.Tensor:
+        """The video side of the matching head for retrieval: encoder forward in eval mode, the aggregation rows, v_proj when the
+        head has one -> a new fp32 [B, text_encoder.dim] tensor.  NOT normalised (the retrieval kernels normalise); no autograd.
+        Refuses what the match task refuses (check_task)."""
+        self.check_task("match")
+        feats, mask = self._video_inputs(video_feats, video_masks)
+        if not self._ps.intact():
+            self._build_flat()
+        self._ps.refresh_shadow()
+        mem = self.video_encoder._engine().forward(feats, mask, False)
+        B, Te = first_input(feats).shape[0], memory_len(feats)
+        mt = self.matching
+        agg = ops.match_agg_fwd(mem, torch.empty(B, mem.shape[1], dtype=torch.float32, device=mem.device), B, Te)
+        if mt.v_proj is None:
+            return agg
+        out = torch.empty(B, mt.vt_shape[1], dtype=torch.float32, device=mem.device)
+        ops.gemm(agg, mt.v_proj.weight.data, out, bias=mt.v_proj.bias.data)
+        return out
+
     def cross_forward(self, video_feats, video_masks, captions, text_feats=None):
         """MMT4Caption.py:135-147 of the reference: (loss_beta * cap_loss + (1 - loss_beta) * match_loss, cap_loss, match_loss);
         the two task losses come back detached."""

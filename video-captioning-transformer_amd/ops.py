@@ -855,6 +855,52 @@ def match_loss(text, vid, loss_out, workspace, *, kind: str = "CSL", temp=None, 
     return loss_out
 
 
+def retrieval_workspace_bytes(Nt: int, Nv: int, Dt: int, mode: str = "plain") -> int:
+    """Bytes of caller-owned workspace ops.retrieval_ranks needs (include/vct_hip.h); raises for a shape the kernels do not take."""
+    if mode not in L.RETRIEVAL_MODE:
+        raise ValueError(f"retrieval: mode {mode!r}: 'plain' or 'dual_softmax'")
+    n = int(L.load().vct_retrieval_workspace_bytes(int(Nt), int(Nv), int(Dt), L.RETRIEVAL_MODE[mode]))
+    if n <= 0:
+        raise ValueError(f"retrieval: {Nt} texts x {Nv} videos x dimension {Dt} is outside the kernels' range "
+                         f"(1 <= texts, videos <= 2^20, dimension a multiple of 4 up to 1024)")
+    return n
+
+
+def retrieval_ranks(text, vid, gt, ranks_t2v, ranks_v2t, out, workspace, *, mode: str = "plain", tau=None, phases=None):
+    """Text->video and video->text ranks over a whole split and their statistics (include/vct_hip.h, vct_retrieval_ranks).  text
+    fp32 [Nt, Dt] / vid fp32 [Nv, Dt] row-major views (row stride a multiple of 4), gt int32 [Nt]; ranks_t2v int32 [Nt], ranks_v2t
+    int32 [Nv], out fp64 [12]; tau: fp32 device scalar, required exactly for mode 'dual_softmax'; workspace: >=
+    retrieval_workspace_bytes(Nt, Nv, Dt, mode) bytes; phases: None (everything) or an iterable of _lib.RETRIEVAL_PHASE names."""
+    if mode not in L.RETRIEVAL_MODE:
+        raise ValueError(f"retrieval: mode {mode!r}: 'plain' or 'dual_softmax'")
+    if (mode == "dual_softmax") != (tau is not None):
+        raise ValueError("retrieval: tau (an fp32 device scalar) is required for mode 'dual_softmax' and only for it")
+    if text.dim() != 2 or vid.dim() != 2 or text.shape[1] != vid.shape[1]:
+        raise ValueError(f"retrieval: text [Nt, Dt] and video [Nv, Dt] features expected, got {tuple(text.shape)} and {tuple(vid.shape)}")
+    Nt, Dt = text.shape
+    Nv = vid.shape[0]
+    for t in (text, vid, tau):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError("retrieval: text, vid and tau are fp32")
+    if text.stride(1) != 1 or vid.stride(1) != 1:
+        raise ValueError("retrieval: text and vid rows must be contiguous")
+    for t, n, what in ((gt, Nt, "gt"), (ranks_t2v, Nt, "ranks_t2v"), (ranks_v2t, Nv, "ranks_v2t")):
+        if t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous():
+            raise ValueError(f"retrieval: {what} must be contiguous int32 [{n}], got {t.dtype} {tuple(t.shape)}")
+    if out.dtype != torch.float64 or tuple(out.shape) != (12,) or not out.is_contiguous():
+        raise ValueError("retrieval: out must be contiguous fp64 [12]")
+    retrieval_workspace_bytes(Nt, Nv, Dt, mode)                    # (raises for a shape outside the kernels' range)
+    d = L.RetrievalDesc()
+    d.Nt, d.Nv, d.Dt, d.mode = Nt, Nv, Dt, L.RETRIEVAL_MODE[mode]
+    d.text, d.ld_text, d.vid, d.ld_vid = text.data_ptr(), (text.stride(0) if Nt > 1 else max(Dt, text.stride(0))), vid.data_ptr(), \
+        (vid.stride(0) if Nv > 1 else max(Dt, vid.stride(0)))
+    d.gt, d.tau, d.ranks_t2v, d.ranks_v2t, d.out = gt.data_ptr(), L.ptr(tau), ranks_t2v.data_ptr(), ranks_v2t.data_ptr(), out.data_ptr()
+    d.workspace, d.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    d.phases = 0 if phases is None else sum(L.RETRIEVAL_PHASE[p] for p in set(phases))
+    L.check(L.load().vct_retrieval_ranks(L.C.byref(d), L.stream_ptr()), "vct_retrieval_ranks")
+    return out
+
+
 def _agg_desc(t, B, Te):
     if t.dim() != 2 or t.shape[0] != B * Te or not t.is_contiguous():
         raise ValueError(f"matching aggregation rows: contiguous [B*Te, d] = [{B * Te}, d] expected, got {tuple(t.shape)}")
