@@ -33,7 +33,10 @@ extern "C" {
 #define VCT_ABI_VERSION 16
 
 enum { VCT_F32 = 0, VCT_BF16 = 1 };
-enum { VCT_ACT_NONE = 0, VCT_ACT_GELU = 1, VCT_ACT_RELU = 2 };
+enum { VCT_ACT_NONE = 0, VCT_ACT_GELU = 1, VCT_ACT_RELU = 2,
+       VCT_ACT_QUICK_GELU = 3 /* x * sigmoid(1.702 x), CLIP's activation.  vct_gemm's forward form only (ta = 0, tb = 1, no dact_src;
+                                 anything else is VCT_E_ARG): it is compiled into no other kernel, and the `act` fields of the other
+                                 descriptors (layer, decode) take NONE / GELU / RELU as before */ };
 enum {
   VCT_OK = 0,
   VCT_E_ARG = -1,      /* null pointer / bad enum */
@@ -474,6 +477,24 @@ int vct_hmm_mix_bwd(const vct_hmm_mix_desc* d, void* stream);
 int vct_embed_fwd(int dtype, int B, int S, int d, const int64_t* ids, int64_t id_batch_stride,
                   const void* table, const float* pos, void* x, const uint32_t* seed, uint32_t site,
                   float p_drop, void* stream);
+/* ---------------------------------------------------------------------------------------------
+ * The frozen CLIP text tower (text.py): the two kernels that the rest of the library cannot express.  Forward only.
+ * vct_preln_fwd: y[M, d] = LayerNorm(x[M, d]) (eps 1e-5, biased variance, affine).  x is the FP32 residual stream of a pre-LN stack,
+ *   y has out_dtype (VCT_F32 | VCT_BF16); no statistics are saved.  replaces: `ln_1` / `ln_2` of CLIP's ResidualAttentionBlock
+ *   (clip/model.py, as reached from the reference's model/TextEncoder.py).
+ * vct_text_pool: per caption b, e_b = the FIRST index of the maximum of ids[b, 0 .. Lids) (CLIP: `text.argmax(dim=-1)`, the EOT token
+ *   has the largest id); y[b] = LayerNorm(x[b * L + e_b]) in out_dtype (gamma / beta = ln_final); eot[b] = e_b (int32).
+ *   ids: int64 [B, ld_ids]; x: fp32 [B * L, d], the stream of the first L <= Lids positions.  e_b >= L (the caller trimmed behind the
+ *   EOT) sets *err = 1 (device int32, never cleared here) and writes a zero row -- the caller reads err when it chooses to.
+ *   replaces: `x[arange(B), text.argmax(-1)]` between ln_final and text_projection (clip/model.py, encode_text).
+ * d a multiple of 4 (VCT_E_ALIGN) up to 1024 (VCT_E_SHAPE); M, B, L >= 1, Lids >= L, ld_ids >= Lids (VCT_E_SHAPE); x / gamma / beta and
+ * an fp32 y 16-byte, a bf16 y and ids 8-byte, eot / err 4-byte aligned (VCT_E_ALIGN); NULL operand / bad dtype: VCT_E_ARG.  All
+ * before any device use.
+ * --------------------------------------------------------------------------------------------- */
+int vct_preln_fwd(int out_dtype, int M, int d, const float* x, const float* gamma, const float* beta, void* y, void* stream);
+int vct_text_pool(int out_dtype, int B, int L, int Lids, int d, const int64_t* ids, int64_t ld_ids, const float* x,
+                  const float* gamma, const float* beta, void* y, int32_t* eot, int32_t* err, void* stream);
+
 int vct_embed_bwd(int dtype, int B, int S, int d, int V, const int64_t* ids, int64_t id_batch_stride,
                   int64_t pad_id, const void* dx, float* dtable, int32_t* id_ws, int64_t id_ws_ints, int incremental,
                   const uint32_t* seed, uint32_t site, float p_drop, void* stream);

@@ -13,7 +13,7 @@ F32, BF16 = 0, 1
 ABI_VERSION = 16
 GEMM_GROUP_MAX = 8
 GEMM_ROUTE_INTS = 17
-ACT = {"none": 0, None: 0, "gelu": 1, "relu": 2}
+ACT = {"none": 0, None: 0, "gelu": 1, "relu": 2, "quick_gelu": 3}
 _ERR = {-1: "VCT_E_ARG (null pointer / bad enum)", -2: "VCT_E_SHAPE (unsupported shape)",
         -3: "VCT_E_ALIGN (leading dimension / alignment)", -4: "VCT_E_WORKSPACE (workspace too small)"}
 
@@ -256,6 +256,8 @@ _SIGS = {
     "vct_scale": (C.c_int, [vp, i64, f32, vp]),
     "vct_axpby": (C.c_int, [vp, vp, f32, vp, f32, i64, vp]),
     "vct_embed_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, vp, vp, vp, u32, f32, vp]),
+    "vct_preln_fwd": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
+    "vct_text_pool": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
     "vct_embed_bwd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, i64, vp, vp, vp, i64, C.c_int, vp, u32, f32, vp]),
     "vct_embed_bwd_live": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, i64, vp, vp, vp, i64, C.c_int, vp, u32, f32, vp, vp]),
     "vct_embed_live_rebuild": (C.c_int, [i32, i32, vp, vp, vp, vp, vp]),

@@ -55,7 +55,14 @@ __device__ __forceinline__ float dgelu_f(float x) {
   const float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);
   return cdf + x * pdf;
 }
-__device__ __forceinline__ float act_f(int act, float x) {
+// CLIP's QuickGELU: x * sigmoid(1.702 x).  Forward only (the text tower is frozen): there is no dact_f case, and vct_gemm refuses a
+// descriptor that asks for its derivative.  x -> -inf: exp overflows to +inf and the quotient is -0, the limit.
+__device__ __forceinline__ float quick_gelu_f(float x) { return x / (1.0f + expf(-1.702f * x)); }
+__device__ __forceinline__ float quick_gelu_fast_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-1.702f * x)); }
+// QG: whether VCT_ACT_QUICK_GELU is compiled into this call site.  Only the forward (NT) GEMM routes ask for it (vct_gemm refuses the
+// activation everywhere else), so every other kernel's code is what it was before the activation existed.
+template <bool QG = false> __device__ __forceinline__ float act_f(int act, float x) {
+  if constexpr (QG) { if (act == VCT_ACT_QUICK_GELU) return quick_gelu_f(x); }
   return act == VCT_ACT_GELU ? gelu_f(x) : (act == VCT_ACT_RELU ? fmaxf(x, 0.0f) : x);
 }
 __device__ __forceinline__ float dact_f(int act, float x) {
@@ -92,9 +99,10 @@ __device__ __forceinline__ void erf_cdf_pdf_fast2(const vf2 x, vf2& cdf, vf2& pd
   cdf = sg * 0.5f + 0.5f;
   pdf = e * 0.3989422804014327f;
 }
-__device__ __forceinline__ vf2 act_fast_f2(int act, const vf2 x) {
+template <bool QG = false> __device__ __forceinline__ vf2 act_fast_f2(int act, const vf2 x) {
   if (act == VCT_ACT_GELU) { vf2 c, d; erf_cdf_pdf_fast2(x, c, d); return x * c; }
   if (act == VCT_ACT_RELU) { vf2 r; r[0] = fmaxf(x[0], 0.0f); r[1] = fmaxf(x[1], 0.0f); return r; }
+  if constexpr (QG) { if (act == VCT_ACT_QUICK_GELU) { vf2 r; r[0] = quick_gelu_fast_f(x[0]); r[1] = quick_gelu_fast_f(x[1]); return r; } }
   return x;
 }
 __device__ __forceinline__ vf2 dact_fast_f2(int act, const vf2 x) {
@@ -103,8 +111,9 @@ __device__ __forceinline__ vf2 dact_fast_f2(int act, const vf2 x) {
   if (act == VCT_ACT_RELU) { r[0] = x[0] > 0.0f ? 1.0f : 0.0f; r[1] = x[1] > 0.0f ? 1.0f : 0.0f; }
   return r;
 }
-__device__ __forceinline__ float act_fast_f(int act, float x) {
+template <bool QG = false> __device__ __forceinline__ float act_fast_f(int act, float x) {
   if (act == VCT_ACT_GELU) { float c, d; erf_cdf_pdf_fast(x, c, d); return x * c; }
+  if constexpr (QG) { if (act == VCT_ACT_QUICK_GELU) return quick_gelu_fast_f(x); }
   return act == VCT_ACT_RELU ? fmaxf(x, 0.0f) : x;
 }
 __device__ __forceinline__ float dact_fast_f(int act, float x) {

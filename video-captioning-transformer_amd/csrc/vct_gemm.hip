@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmP p) {
         for (int q = 0; q < VO; q++) {
           float x = v[q] + bvec[c][q];
           pv.e[q] = from_f<TO>(x);
-          x = act_f(p.act, x);
+          x = act_f<true>(p.act, x);
           if (has_d) x *= dact_f(p.dact_kind, to_f<TO>(dv.e[q]));
           x *= drop_mult(dr, (uint32_t)row * (uint32_t)p.N + (uint32_t)(col + q));
           if (has_a) x += to_f<TO>(av.e[q]);
@@ -261,7 +261,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmP p) {
           if (col + q >= p.N) break;
           float x = v[q] + bvec[c][q];
           if (preact != nullptr) preact[(size_t)row * p.ld_preact + col + q] = from_f<TO>(x);
-          x = act_f(p.act, x);
+          x = act_f<true>(p.act, x);
           if (dact != nullptr) x *= dact_f(p.dact_kind, to_f<TO>(dact[(size_t)row * p.ld_dact + col + q]));
           x *= drop_mult(dr, (uint32_t)row * (uint32_t)p.N + (uint32_t)(col + q));
           if (addend != nullptr) x += to_f<TO>(addend[(size_t)row * p.ld_addend + col + q]);
@@ -426,6 +426,8 @@ static int check_desc(const vct_gemm_desc* d) {
   if (d->lda % vec || d->ldb % vec) return VCT_E_ALIGN;
   if (((uintptr_t)d->A & 15) || ((uintptr_t)d->B & 15)) return VCT_E_ALIGN;
   if (d->dact_src != nullptr && d->act == VCT_ACT_NONE) return VCT_E_ARG;  // dact needs the activation kind
+  // QuickGELU: the forward (NT) form only -- no derivative exists and the NN / TN kernels do not carry the activation
+  if (d->act == VCT_ACT_QUICK_GELU && (d->dact_src != nullptr || d->ta != 0 || d->tb != 1)) return VCT_E_ARG;
   // bf16 path: the bias gradient is fused into the weight-gradient form only (dW = A^T B, fp32 out)
   if (d->bias_grad != nullptr && d->dtype == VCT_BF16 && !(d->ta == 1 && d->tb == 0 && d->out_dtype == VCT_F32)) return VCT_E_ARG;
   if (d->adam != nullptr) {

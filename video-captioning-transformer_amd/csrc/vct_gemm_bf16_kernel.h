@@ -213,6 +213,7 @@ __device__ __forceinline__ bf16x8 frag2(const unsigned char* lds, int r_base, in
 template <typename TO, int TA, int TB, int BM, int BN, int NBUF, int WGM, int WGN>
 __device__ __forceinline__ void gemm_bf16_v2_body(const GemmP& p, const int bid, const int zid, const bool direct = false) {
   constexpr bool A_MC = (TA == 1), B_MC = (TB == 0);
+  constexpr bool QGELU = (TA == 0 && TB == 1);   // VCT_ACT_QUICK_GELU: forward (NT) products only, see act_f in vct_common.h
   constexpr bool KSPLIT = A_MC && B_MC;
   constexpr int NW = WGM * WGN, NT = 64 * NW;         // waves / threads per workgroup
   constexpr bool DMA_IL = VCT_GEMM_DMA_IL(TA, TB, BM, BN, NW);   // interleave the next tile's DMA with this tile's MFMAs
@@ -564,7 +565,7 @@ __device__ __forceinline__ void gemm_bf16_v2_body(const GemmP& p, const int bid,
       for (int q = 0; q < VO; q += 2) {                      // pairs: packed fp32 arithmetic in the activation (vct_common.h)
         vf2 x = {v[q] + bv[q], v[q + 1] + bv[q + 1]};
         pv.e[q] = from_f<TO>(x[0]); pv.e[q + 1] = from_f<TO>(x[1]);
-        x = act_fast_f2(p.act, x);
+        x = act_fast_f2<QGELU>(p.act, x);
         if (has_d) x *= dact_fast_f2(p.dact_kind, vf2{to_f<TO>(dv.e[q]), to_f<TO>(dv.e[q + 1])});
         float dm2[2];
         drop_mults<2>(dr, (uint32_t)row * (uint32_t)p.N + (uint32_t)(col + q), dm2);
@@ -593,7 +594,7 @@ __device__ __forceinline__ void gemm_bf16_v2_body(const GemmP& p, const int bid,
         if (col + q >= p.N) break;
         float x = v[q] + bv[q];
         if (preact != nullptr) preact[(size_t)row * p.ld_preact + col + q] = from_f<TO>(x);
-        x = act_fast_f(p.act, x);
+        x = act_fast_f<QGELU>(p.act, x);
         if (dact != nullptr) x *= dact_fast_f(p.dact_kind, to_f<TO>(dact[(size_t)row * p.ld_dact + col + q]));
         x *= drop_mult(dr, (uint32_t)row * (uint32_t)p.N + (uint32_t)(col + q));
         if (addend != nullptr) x += to_f<TO>(addend[(size_t)row * p.ld_addend + col + q]);

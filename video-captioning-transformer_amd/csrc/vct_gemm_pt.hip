@@ -253,7 +253,7 @@ __global__ __launch_bounds__(512, 4) void gemm_pt_kernel(const GemmP p) {
               for (int qq = 0; qq < 8; qq += 2) {            // pairs: packed fp32 arithmetic in the activation (vct_common.h)
                 vf2 x = {v[qq] + bv[qq], v[qq + 1] + bv[qq + 1]};
                 pv.e[qq] = f2bf(x[0]); pv.e[qq + 1] = f2bf(x[1]);
-                x = act_fast_f2(p.act, x);
+                x = act_fast_f2<true>(p.act, x);
                 if (has_d) x *= dact_fast_f2(p.dact_kind, vf2{bf2f(dv.e[qq]), bf2f(dv.e[qq + 1])});
                 float dm2[2];
                 drop_mults<2>(dr, (uint32_t)row * (uint32_t)p.N + (uint32_t)(col + qq), dm2);
@@ -268,7 +268,7 @@ __global__ __launch_bounds__(512, 4) void gemm_pt_kernel(const GemmP p) {
                 if (col + qq >= p.N) break;
                 float x = v[qq] + (p.bias != nullptr ? p.bias[col + qq] : 0.0f);
                 if (preact != nullptr) preact[(size_t)row * p.ld_preact + col + qq] = f2bf(x);
-                x = act_fast_f(p.act, x);
+                x = act_fast_f<true>(p.act, x);
                 if (dact != nullptr) x *= dact_fast_f(p.dact_kind, bf2f(dact[(size_t)row * p.ld_dact + col + qq]));
                 x *= drop_mult(dr, (uint32_t)row * (uint32_t)p.N + (uint32_t)(col + qq));
                 if (addend != nullptr) x += bf2f(addend[(size_t)row * p.ld_addend + col + qq]);

@@ -172,7 +172,7 @@ __global__ __launch_bounds__(512) void gemm_skinny_nt_kernel(const SkinnyP p) {
     for (int r = 0; r < 4; r++) {
       if (col + r >= p.N) break;
       float x = v[r] + (p.bias != nullptr ? p.bias[col + r] : 0.0f);
-      x = act_fast_f(p.act, x);
+      x = act_fast_f<true>(p.act, x);
       if (addend != nullptr) {
         if (add32) x += full ? af[r] : addf[(size_t)row * p.ld_addend + col + r];
         else if (add16) x += full ? af[r] : bf2f(addh[(size_t)row * p.ld_addend + col + r]);

@@ -130,6 +130,23 @@ class MMT4Caption(nn.Module):
         self._pending_enc_bwd = None      # train_step_kernels(defer_join=True): the encoder backward, not enqueued yet
         self._mem = None                  # the encoder memory of the last caption forward
         self._build_flat()
+        if model_config.get("text_enc_weights"):
+            # optional: a CLIP state dict on disk -> the text tower on our kernels (text.py).  It still needs a tokenizer
+            # (tower.tokenize = clip.tokenize) before it can take strings; ids work as they are.
+            from ..text import ClipTextTower
+            self.install_text_encoder(ClipTextTower.from_file(model_config["text_enc_weights"], device, compute_dtype=self.compute_dtype))
+
+    def install_text_encoder(self, tower):
+        """Make `tower` (text.ClipTextTower) the producer of the matching task's sentence features: model.text_encoder(captions)
+        then runs it.  Its weights stay outside this module's parameters and state_dict (the reference's TextEncoder is no module)."""
+        if int(tower.dim) != int(self.text_encoder.dim):
+            raise ValueError(f"the text tower produces {tower.dim}-dimensional features, the model's text encoder (and the matching "
+                             f"head) is sized for {self.text_encoder.dim}: set model.text_enc_dim")
+        mine, theirs = torch.device(self.device), torch.device(tower.device)
+        if theirs.type != mine.type or (None not in (mine.index, theirs.index) and mine.index != theirs.index):
+            raise ValueError(f"the text tower is on {tower.device}, the model on {self.device}")
+        self.text_encoder.backend = tower
+        return tower
 
     # ---- flat parameter storage --------------------------------------------------------------------
     def _build_flat(self):

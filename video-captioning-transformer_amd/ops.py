@@ -538,6 +538,31 @@ def embed_fwd(ids, S, table, pos, x, dropout: Drop = None):
     return x
 
 
+def preln_fwd(x, gamma, beta, y):
+    """y = LayerNorm(x): x the fp32 residual stream [M, d] of a pre-LN stack, y [M, d] fp32 or bf16 (include/vct_hip.h, vct_preln_fwd)."""
+    M, dm = x.shape
+    assert x.dtype == torch.float32 and x.is_contiguous() and y.is_contiguous() and tuple(y.shape) == (M, dm)
+    assert gamma.dtype == beta.dtype == torch.float32 and gamma.numel() == beta.numel() == dm
+    L.check(L.load().vct_preln_fwd(L.dtype_code(y.dtype), M, dm, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
+                                   L.stream_ptr()), "vct_preln_fwd")
+    return y
+
+
+def text_pool(ids, x, S, gamma, beta, y, eot, err):
+    """y[b] = LayerNorm(x[b * S + e_b]), e_b = first index of the maximum of ids[b] (all columns of ids are scanned), eot[b] = e_b.
+    ids int64 [B, >= S]; x fp32 [B * S, d]; y [B, d] fp32 or bf16; eot int32 [B]; err int32 [1], raised when an e_b lies behind S
+    (include/vct_hip.h, vct_text_pool)."""
+    B, dm = y.shape
+    assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.shape[0] == B and ids.stride(1) == 1 and ids.shape[1] >= S
+    assert x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == (B * S, dm) and y.is_contiguous()
+    assert gamma.dtype == beta.dtype == torch.float32 and gamma.numel() == beta.numel() == dm
+    assert eot.dtype == torch.int32 and eot.numel() >= B and err.dtype == torch.int32 and err.numel() >= 1
+    L.check(L.load().vct_text_pool(L.dtype_code(y.dtype), B, S, ids.shape[1], dm, ids.data_ptr(), ids.stride(0), x.data_ptr(),
+                                   gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), eot.data_ptr(), err.data_ptr(), L.stream_ptr()),
+            "vct_text_pool")
+    return y
+
+
 _embed_ws = {}
 _embed_ws_retired = []
 _embed_live = {}

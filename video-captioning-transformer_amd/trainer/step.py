@@ -84,7 +84,9 @@ class CaptionTrainer:
         """match / cross: train_step_kernels_* then the optimizer over the task's range (gradients stay valid: model.grads_valid)."""
         m = self.model
         if text_feats is None:
-            raise ValueError(f"task {self.task!r}: pass text_feats (fp32 [B, {m.text_encoder.dim}] on the model's device)")
+            if m.text_encoder.backend is None or ids is None:
+                raise ValueError(f"task {self.task!r}: pass text_feats (fp32 [B, {m.text_encoder.dim}] on the model's device)")
+            text_feats = m.text_encoder(ids)        # an installed encoder (MMT4Caption.install_text_encoder) takes the captions
         ops.tap("step", 0)
         if not self._fused:
             m._ps.masters_written()
