@@ -1,7 +1,7 @@
 """fp64 torch reference of the four block kinds of vct_decode_block (include/vct_hip.h), shared by tests/test_decode_block_gpu.py:
 the batch-1 decode step of one nn.TransformerDecoderLayer cut into self-attention, cross-attention and feed-forward blocks that
 each return the PARTIAL vectors of their second product (one per head / per 64 hidden units), and the generator with the greedy
-token.  Written from the operation's definition, independently of ops.py and the engine: weights are taken in nn.Linear's
+token.  Written from the operation's definition, independently of the ops package and the engine: weights are taken in nn.Linear's
 natural [out, in] layout, nothing is rounded, everything runs on the CPU.  `dtype` exists so that the same formulas can be
 evaluated in fp32 (what a summation-order-free fp32 implementation would give against fp64)."""
 import math

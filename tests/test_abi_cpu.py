@@ -1,5 +1,6 @@
 """CPU-side checks of the C-ABI boundary: the library builds/loads without a GPU and exports every
-symbol include/vct_hip.h declares (no compute calls here)."""
+symbol include/vct_hip.h declares (no compute calls here); the ctypes mirror of the header (structs, signatures, constants)
+agrees with the C compiler's reading of it."""
 import ctypes
 import os
 import re
@@ -97,37 +98,138 @@ def test_new_entry_points_validate_arguments(lib_path):
     assert lib.vct_add_ln_ln_bwd(1, 8, 64, *([None] * 15), 0, 0.0, None) == -1
 
 
-def test_descriptor_structs_match_the_c_header(tmp_path):
-    """ctypes mirrors of the descriptor structs must have the C compiler's size and field offsets."""
+# ---- the hand-written ctypes mirror (vct_amd/_lib.py) against the header, exhaustively: every struct field, every signature, every
+# constant.  Two gcc runs on the header; the library is not needed. ---------------------------------------------------------------
+def _mirror_structs():
     from vct_amd import _lib
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = tmp_path / "sz.c"
-    src.write_text('''#include <stdio.h>
-#include <stddef.h>
-#include "vct_hip.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(vct_gemm_desc), offsetof(vct_gemm_desc, workspace), offsetof(vct_gemm_desc, tile_counters),
-         sizeof(vct_attn_desc), offsetof(vct_attn_desc, d_o), offsetof(vct_attn_desc, q_bs));
-  printf("%zu %zu %zu %zu %zu %zu %zu\\n", sizeof(vct_layer_ss_desc), offsetof(vct_layer_ss_desc, wpk), offsetof(vct_layer_ss_desc, n2),
-         offsetof(vct_layer_ss_desc, key_pad), offsetof(vct_layer_ss_desc, site_n3), sizeof(vct_ss_pack_seg), offsetof(vct_ss_pack_seg, dst_chunk));
-  printf("%zu %zu %zu %zu %zu\\n", sizeof(vct_layer_ss_bwd_desc), offsetof(vct_layer_ss_bwd_desc, wpk), offsetof(vct_layer_ss_bwd_desc, n3),
-         offsetof(vct_layer_ss_bwd_desc, key_pad), offsetof(vct_layer_ss_bwd_desc, site_n3));
-  printf("%zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(vct_gemm_adam), offsetof(vct_gemm_adam, shadow), offsetof(vct_gemm_adam, pk_stream),
-         offsetof(vct_gemm_adam, pk_chunk0), offsetof(vct_gemm_adam, store_grad), offsetof(vct_gemm_adam, step), offsetof(vct_gemm_desc, adam),
-         sizeof(vct_adam_range));
-  return 0;
-}''')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(root, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    G, A = _lib.GemmDesc, _lib.AttnDesc
-    S, P = _lib.LayerSsDesc, _lib.SsPackSeg
-    assert got == [ctypes.sizeof(G), G.workspace.offset, G.tile_counters.offset, ctypes.sizeof(A), A.d_o.offset, A.q_bs.offset,
-                   ctypes.sizeof(S), S.wpk.offset, S.n2.offset, S.key_pad.offset, S.site_n3.offset, ctypes.sizeof(P), P.dst_chunk.offset,
-                   ctypes.sizeof(_lib.LayerSsBwdDesc), _lib.LayerSsBwdDesc.wpk.offset, _lib.LayerSsBwdDesc.n3.offset,
-                   _lib.LayerSsBwdDesc.key_pad.offset, _lib.LayerSsBwdDesc.site_n3.offset,
-                   ctypes.sizeof(_lib.GemmAdam), _lib.GemmAdam.shadow.offset, _lib.GemmAdam.pk_stream.offset, _lib.GemmAdam.pk_chunk0.offset,
-                   _lib.GemmAdam.store_grad.offset, _lib.GemmAdam.step.offset, G.adam.offset, ctypes.sizeof(_lib.AdamRange)]
+    return [v for v in vars(_lib).values() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure]
+
+
+def _layout(S, c_expr=False):
+    """{"T": sizeof, "T.f offset": offset, "T.f size": size, ...} of the ctypes mirror S of the C struct T -- or, with c_expr, the C
+    expressions of the same numbers."""
+    T, fields = S._c_name_, [f[0] for f in S._fields_]
+    if c_expr:
+        return {T: f"sizeof({T})", **{f"{T}.{f} offset": f"offsetof({T}, {f})" for f in fields},
+                **{f"{T}.{f} size": f"sizeof((({T}*)0)->{f})" for f in fields}}
+    return {T: ctypes.sizeof(S), **{f"{T}.{f} offset": getattr(S, f).offset for f in fields},
+            **{f"{T}.{f} size": getattr(S, f).size for f in fields}}
+
+
+def _layout_mismatches(S, from_c):
+    """The entries of S's layout ("struct", "struct.field offset", "struct.field size") that are not the C compiler's."""
+    return [k for k, v in _layout(S).items() if from_c.get(k) != v]
+
+
+@pytest.fixture(scope="module")
+def from_c(tmp_path_factory):
+    """One C program against the header prints every C_CONSTANTS name and the layout of every mirrored struct: {name: number}."""
+    from vct_amd import _lib
+    exprs = {k: k for k in _lib.C_CONSTANTS}
+    for S in _mirror_structs():
+        if "_c_name_" in S.__dict__:                       # (a mirror without a name fails test_every_struct_field_... by name)
+            exprs.update(_layout(S, c_expr=True))
+    d = tmp_path_factory.mktemp("abi")
+    (d / "abi.c").write_text('#include <stdio.h>\n#include <stddef.h>\n#include "vct_hip.h"\nint main(void) {\n'
+                             + "".join(f'  printf("%lld\\n", (long long)({e}));\n' for e in exprs.values()) + "  return 0;\n}\n")
+    subprocess.run(["gcc", "-I", os.path.dirname(HDR), str(d / "abi.c"), "-o", str(d / "abi")], check=True)
+    out = subprocess.run([str(d / "abi")], capture_output=True, text=True, check=True).stdout.split()
+    assert len(out) == len(exprs)
+    return dict(zip(exprs, map(int, out)))
+
+
+def test_every_struct_field_matches_the_c_header(from_c):
+    """Every ctypes.Structure of _lib names its C struct, every typedef struct of the header has a mirror, and sizeof of each struct
+    and offsetof + sizeof of each field (arrays and nested structs included) are the C compiler's."""
+    structs = _mirror_structs()
+    unnamed = [S.__name__ for S in structs if "_c_name_" not in S.__dict__]
+    assert not unnamed, f"ctypes mirrors without _c_name_: {unnamed}"
+    hdr = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
+    assert sorted(S._c_name_ for S in structs) == sorted(re.findall(r"typedef\s+struct\s+(\w+)", hdr))
+    bad = [k for S in structs for k in _layout_mismatches(S, from_c)]
+    assert not bad, f"ctypes layout differs from the header at: {bad}"
+    assert len(structs) >= 25 and sum(len(S._fields_) for S in structs) >= 489
+
+
+_SCALARS = {"int": "i32", "int32_t": "i32", "int64_t": "i64", "uint32_t": "u32", "float": "f32", "double": "f64"}
+
+
+def _c_type(s):
+    """Class of a C type as gcc prints it: i32 / i64 / u32 / f32 / f64, "ptr:<pointee>", anything else as spelled."""
+    s = s.replace("const ", "").strip()
+    if "(*)" in s:
+        return "ptr:fn"
+    return "ptr:" + _c_type(s[:-1]) if s.endswith("*") else _SCALARS.get(s, s)
+
+
+def _py_type(t):
+    """The same class of a ctypes type; c_void_p / c_char_p are the untyped "ptr", which stands for any C pointer."""
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p):
+        return "ptr"
+    if issubclass(t, ctypes.Structure):
+        return t._c_name_
+    if issubclass(t, ctypes._Pointer):
+        return "ptr:" + _py_type(t._type_)
+    return {ctypes.c_int32: "i32", ctypes.c_int64: "i64", ctypes.c_uint32: "u32", ctypes.c_float: "f32", ctypes.c_double: "f64"}[t]
+
+
+def _sig_mismatches(name, sig, proto):
+    """What differs between a _SIGS entry (restype, argtypes) and the header's prototype (return type, [argument types]), by
+    position.  POINTER(S) needs the C pointee S._c_name_; a struct pointer in C needs POINTER of its mirror or plain c_void_p."""
+    def same(py, c):
+        return py == c or (py.endswith("ptr") and c.startswith(py + ":"))
+    bad = [] if same(_py_type(sig[0]), _c_type(proto[0])) else [f"{name}: returns {proto[0]} in C, {_py_type(sig[0])} in ctypes"]
+    if len(sig[1]) != len(proto[1]):
+        return bad + [f"{name}: {len(proto[1])} arguments in C, {len(sig[1])} in ctypes"]
+    return bad + [f"{name}: argument {i}: {c} in C, {_py_type(a)} in ctypes" for i, (a, c) in enumerate(zip(sig[1], proto[1]))
+                  if not same(_py_type(a), _c_type(c))]
+
+
+def test_every_signature_matches_the_c_header(tmp_path):
+    """gcc's own reading of the header (-aux-info: one normalised prototype per function) against _SIGS: the same functions, and
+    for each the return type, the number of arguments and every argument's class."""
+    from vct_amd import _lib
+    (tmp_path / "tu.c").write_text('#include "vct_hip.h"\n')
+    subprocess.run(["gcc", "-fsyntax-only", "-aux-info", str(tmp_path / "tu.X"), "-I", os.path.dirname(HDR), str(tmp_path / "tu.c")], check=True)
+    protos = {}
+    for ret, name, args in re.findall(r"extern (.+?)\b(vct_\w+) \((.*)\);", (tmp_path / "tu.X").read_text()):
+        protos[name] = (ret.strip(), [] if args == "void" else args.split(", "))
+    assert sorted(protos) == sorted(_lib._SIGS) and len(protos) >= 102
+    bad = [m for name, sig in _lib._SIGS.items() for m in _sig_mismatches(name, sig, protos[name])]
+    assert not bad, bad
+
+
+def test_constants_match_the_c_header(from_c):
+    from vct_amd import _lib
+    bad = {k: (v, from_c[k]) for k, v in _lib.C_CONSTANTS.items() if from_c[k] != v}
+    assert not bad, f"name: (_lib, header) {bad}"
+    assert len(_lib.C_CONSTANTS) >= 39 and _lib.C_CONSTANTS["VCT_ABI_VERSION"] == 16
+
+
+def test_the_mirror_checks_can_fail(from_c):
+    """Wrong mirrors of vct_adam_range (two fields swapped; a field of the wrong width) and a wrong signature (int64_t where the
+    header has float) are reported, by name."""
+    i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
+
+    class Swapped(ctypes.Structure):
+        _c_name_ = "vct_adam_range"
+        _fields_ = [("begin", i64), ("end", i64), ("shadow", i32), ("blk0", i32)]
+
+    class Narrow(ctypes.Structure):
+        _c_name_ = "vct_adam_range"
+        _fields_ = [("begin", i32), ("end", i64), ("blk0", i32), ("shadow", i32)]
+    assert _layout_mismatches(Swapped, from_c) == ["vct_adam_range.shadow offset", "vct_adam_range.blk0 offset"]
+    assert _layout_mismatches(Narrow, from_c) == ["vct_adam_range.begin size"]
+    scale = ("int", ["float *", "int64_t", "float", "void *"])             # vct_scale as gcc prints it
+    assert _sig_mismatches("vct_scale", (ctypes.c_int, [vp, i64, ctypes.c_float, vp]), scale) == []
+    assert _sig_mismatches("vct_scale", (ctypes.c_int, [vp, i64, i64, vp]), scale) == ["vct_scale: argument 2: float in C, i64 in ctypes"]
+    assert _sig_mismatches("vct_scale", (i64, [vp, i64, vp]), scale) == ["vct_scale: returns int in C, i64 in ctypes",
+                                                                         "vct_scale: 4 arguments in C, 3 in ctypes"]
+    gemm = ("int", ["const vct_gemm_desc *", "void *"])
+    assert _sig_mismatches("vct_gemm", (ctypes.c_int, [ctypes.POINTER(Swapped), vp]), gemm) == [
+        "vct_gemm: argument 0: const vct_gemm_desc * in C, ptr:vct_adam_range in ctypes"]
 
 
 def test_layer_ss_entry_points_validate_arguments(lib_path):
@@ -159,7 +261,6 @@ def test_layer_ss_entry_points_validate_arguments(lib_path):
     q.d = 768
     assert lib.vct_layer_ss_bwd(q, 1, None) == -2
     # Adam that also maintains stream-order packed weight copies: a table without a shadow / a misaligned base are argument errors
-    assert ctypes.sizeof(_lib.AdamPackSeg) == 48
     buf = (ctypes.c_float * 16)()
     p = ctypes.addressof(buf)
     assert lib.vct_adam_step_pk(p, p, p, p, None, 8, 1e-3, 0.9, 0.999, 1e-8, 0.0, p, 0, 0, 0, None, p, 1, 0, None) == -1

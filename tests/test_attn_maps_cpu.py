@@ -85,28 +85,6 @@ def test_attn_weights_argument_errors_are_codes(lib):
     assert lib.vct_attn_weights(d, None) == -3
 
 
-def test_descriptor_matches_the_c_header(tmp_path):
-    import ctypes
-    import os
-    import subprocess
-    from vct_amd import _lib
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = tmp_path / "sz.c"
-    src.write_text('''#include <stdio.h>
-#include <stddef.h>
-#include "vct_hip.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu\\n", sizeof(vct_attn_weights_desc), offsetof(vct_attn_weights_desc, w), offsetof(vct_attn_weights_desc, key_pad),
-         offsetof(vct_attn_weights_desc, w_bs), offsetof(vct_attn_weights_desc, pad_id));
-  return 0;
-}''')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(root, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    A = _lib.AttnWeightsDesc
-    assert got == [ctypes.sizeof(A), A.w.offset, A.key_pad.offset, A.w_bs.offset, A.pad_id.offset]
-
-
 def test_fixture_rows_sum_to_one_and_leave_comparable_decode_rows():
     z = load_golden("attnmap_train.npz")
     ids = z["ids"]

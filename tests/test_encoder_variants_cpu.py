@@ -182,25 +182,3 @@ def test_ex_entry_points_reject_bad_arguments():
     assert lib.vct_enc_frontend_ex_bwd(desc(agg=1, temporal=1, emb_rows=512, tidx=A, d_emb=A, temp=None, modal_w=None, dx=A + 8), None) == -3
     assert lib.vct_enc_frontend_ex_bwd(desc(norm=1, gamma=A, mean=A, rstd=A, dpre=A, param_ws=A, temp=None), None) == -1   # the norm recomputes pre
     assert lib.vct_enc_frontend_ex_bwd(desc(norm=1, gamma=A, mean=A, rstd=A), None) == -1               # norm: no dpre / partials buffer
-
-
-def test_struct_mirror_matches_the_c_header(tmp_path):
-    import ctypes
-    import subprocess
-    from vct_amd import _lib
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = tmp_path / "sz.c"
-    src.write_text('''#include <stdio.h>
-#include <stddef.h>
-#include "vct_hip.h"
-#define O(f) offsetof(vct_enc_frontend_ex_desc, f)
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(vct_enc_frontend_ex_desc), O(agg), O(site), O(T), O(u), O(temp), O(seed), O(mean), O(du), O(param_ws));
-  return 0;
-}''')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(root, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    D = _lib.EncFrontendExDesc
-    assert got == [ctypes.sizeof(D), D.agg.offset, D.site.offset, D.T.offset, D.u.offset, D.temp.offset, D.seed.offset, D.mean.offset,
-                   D.du.offset, D.param_ws.offset]

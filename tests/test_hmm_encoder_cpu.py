@@ -241,24 +241,3 @@ def test_mix_entry_points_reject_bad_arguments():
     assert lib.vct_hmm_mix_bwd(desc(dx0=A, acc=None, dy=None, take=None), None) == -1      # the layer-0 form still reads the accumulator
     assert lib.vct_hmm_mix_bwd(desc(dx0=A, init=1, dy=None, take=None), None) == -1        # ... which an earlier launch initialised
     assert lib.vct_hmm_mix_bwd(desc(dx0=A + 4, dy=None, take=None), None) == -3            # dy / take are not needed there
-
-
-def test_struct_mirror_matches_the_c_header(tmp_path):
-    import ctypes
-    import subprocess
-    from vct_amd import _lib
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = tmp_path / "sz.c"
-    src.write_text('''#include <stdio.h>
-#include <stddef.h>
-#include "vct_hip.h"
-#define O(f) offsetof(vct_hmm_mix_desc, f)
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(vct_hmm_mix_desc), O(S), O(init), O(take), O(y), O(x), O(dx), O(acc), O(dx0));
-  return 0;
-}''')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(root, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    D = _lib.HmmMixDesc
-    assert got == [ctypes.sizeof(D), D.S.offset, D.init.offset, D.take.offset, D.y.offset, D.x.offset, D.dx.offset, D.acc.offset, D.dx0.offset]

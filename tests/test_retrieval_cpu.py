@@ -3,7 +3,6 @@ the independent fp64 restatement (tests/retrieval_ref.py), against a torch stabl
 restatement's interval check rejecting five wrong rankers; the conditions the GPU tests' generator must meet, on the restatement
 alone; the refusals of the Python layer and the C-ABI boundary of vct_retrieval_ranks / vct_retrieval_workspace_bytes."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
@@ -11,8 +10,6 @@ import pytest
 import torch
 
 import retrieval_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _host(mode="plain", tau=None):
@@ -240,27 +237,6 @@ def test_new_symbols_header_binding_and_library(lib):
         assert s in decl and s in _lib.exported_symbols() and s in exported, s
     assert sorted(set(decl)) == sorted(set(_lib.exported_symbols()))
     assert lib.vct_abi_version() == _lib.ABI_VERSION == 16              # additive: the version stays
-
-
-def test_descriptor_matches_the_c_header(tmp_path):
-    from vct_amd import _lib
-    src = tmp_path / "sz.c"
-    src.write_text('''#include <stdio.h>
-#include <stddef.h>
-#include "vct_hip.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(vct_retrieval_desc), offsetof(vct_retrieval_desc, text), offsetof(vct_retrieval_desc, gt),
-         offsetof(vct_retrieval_desc, out), offsetof(vct_retrieval_desc, workspace_bytes), offsetof(vct_retrieval_desc, phases));
-  printf("%d %d %d %d\\n", VCT_RETRIEVAL_PLAIN, VCT_RETRIEVAL_DUAL_SOFTMAX, VCT_RETRIEVAL_PH_PREP, VCT_RETRIEVAL_PH_FINISH);
-  return 0;
-}''')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    D = _lib.RetrievalDesc
-    assert got == [ctypes.sizeof(D), D.text.offset, D.gt.offset, D.out.offset, D.workspace_bytes.offset, D.phases.offset,
-                   _lib.RETRIEVAL_MODE["plain"], _lib.RETRIEVAL_MODE["dual_softmax"], _lib.RETRIEVAL_PHASE["prep"],
-                   _lib.RETRIEVAL_PHASE["finish"]]
 
 
 def test_entry_point_refuses_before_any_launch(lib):

@@ -22,20 +22,24 @@ vp, i32, i64, u32, f32, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_
 
 class GemmAdam(C.Structure):
     """include/vct_hip.h, vct_gemm_adam: optimizer epilogue of a weight-gradient GEMM."""
+    _c_name_ = "vct_gemm_adam"
     _fields_ = [("param", vp), ("exp_avg", vp), ("exp_avg_sq", vp), ("shadow", vp), ("ld_shadow", i64),
                 ("pk_stream", vp), ("pk_K", i32), ("pk_mode", i32), ("pk_chunk0", i32 * 4), ("pk_row0", i32), ("store_grad", i32),
                 ("hyper", vp), ("step", vp)]
 
 
 class AdamRange(C.Structure):
+    _c_name_ = "vct_adam_range"
     _fields_ = [("begin", i64), ("end", i64), ("blk0", i32), ("shadow", i32)]
 
 
 class AdamRows(C.Structure):
+    _c_name_ = "vct_adam_rows"
     _fields_ = [("origin", i64), ("row_len", i32), ("nrows", i32), ("live", vp)]
 
 
 class GemmDesc(C.Structure):
+    _c_name_ = "vct_gemm_desc"
     _fields_ = [("dtype", i32), ("out_dtype", i32), ("ta", i32), ("tb", i32), ("M", i32), ("N", i32), ("K", i32),
                 ("act", i32), ("A", vp), ("lda", i64), ("B", vp), ("ldb", i64), ("C", vp), ("ldc", i64),
                 ("bias", vp), ("preact", vp), ("ld_preact", i64), ("addend", vp), ("ld_addend", i64),
@@ -45,6 +49,7 @@ class GemmDesc(C.Structure):
 
 
 class AttnDesc(C.Structure):
+    _c_name_ = "vct_attn_desc"
     _fields_ = [("dtype", i32), ("B", i32), ("H", i32), ("Lq", i32), ("Lk", i32), ("hd", i32), ("causal", i32),
                 ("key_pad_shift", i32), ("q", vp), ("ldq", i64), ("k", vp), ("ldk", i64), ("v", vp), ("ldv", i64),
                 ("o", vp), ("ldo", i64), ("key_pad", vp), ("seed", vp), ("site", u32), ("p_drop", f32),
@@ -55,16 +60,19 @@ class AttnDesc(C.Structure):
 
 class AttnWeightsDesc(C.Structure):
     """include/vct_hip.h, vct_attn_weights_desc: head-averaged attention map."""
+    _c_name_ = "vct_attn_weights_desc"
     _fields_ = [("dtype", i32), ("B", i32), ("H", i32), ("Lq", i32), ("Lk", i32), ("hd", i32), ("causal", i32),
                 ("key_pad_shift", i32), ("q", vp), ("ldq", i64), ("k", vp), ("ldk", i64), ("w", vp), ("ldw", i64),
                 ("key_pad", vp), ("q_bs", i64), ("k_bs", i64), ("w_bs", i64), ("key_ids", vp), ("key_ids_bs", i64), ("pad_id", i64)]
 
 
 class SsNorm(C.Structure):
+    _c_name_ = "vct_ss_norm"
     _fields_ = [("gamma", vp), ("beta", vp), ("y", vp), ("mean", vp), ("rstd", vp)]
 
 
 class LayerSsDesc(C.Structure):
+    _c_name_ = "vct_layer_ss_desc"
     _fields_ = [("dtype", i32), ("B", i32), ("L", i32), ("Lm", i32), ("d", i32), ("H", i32), ("ff", i32), ("act", i32),
                 ("last", i32), ("causal", i32), ("key_pad_shift", i32), ("reserved", i32),
                 ("wpk", vp), ("nchunks", i64), ("x", vp), ("mem", vp), ("b_qkv", vp), ("b_o", vp), ("qkv", vp), ("o", vp), ("a", vp),
@@ -77,18 +85,22 @@ class LayerSsDesc(C.Structure):
 
 
 class SsPackSeg(C.Structure):
+    _c_name_ = "vct_ss_pack_seg"
     _fields_ = [("w", vp), ("ldw", i64), ("nchunks", i32), ("transposed", i32), ("dst_chunk", i64)]
 
 
 class AdamPackSeg(C.Structure):
+    _c_name_ = "vct_adam_pack_seg"
     _fields_ = [("begin", i64), ("end", i64), ("K", i32), ("mode", i32), ("chunk0", i32 * 4), ("stream", vp)]
 
 
 class SsBwdNorm(C.Structure):
+    _c_name_ = "vct_ss_bwd_norm"
     _fields_ = [("gamma", vp), ("mean", vp), ("rstd", vp), ("ws", vp)]
 
 
 class LayerSsBwdDesc(C.Structure):
+    _c_name_ = "vct_layer_ss_bwd_desc"
     _fields_ = [("dtype", i32), ("B", i32), ("L", i32), ("d", i32), ("H", i32), ("ff", i32), ("act", i32), ("last", i32), ("causal", i32),
                 ("key_pad_shift", i32), ("wpk", vp), ("nchunks", i64), ("dy", vp), ("dx", vp), ("y_last", vp),
                 ("x", vp), ("qkv", vp), ("a", vp), ("x1", vp), ("hpre", vp), ("f", vp),
@@ -99,6 +111,7 @@ class LayerSsBwdDesc(C.Structure):
 
 
 class DecodeGemvDesc(C.Structure):
+    _c_name_ = "vct_decode_gemv_desc"
     _fields_ = [("wdtype", i32), ("B", i32), ("N", i32), ("K", i32), ("W", vp), ("ldw", i64), ("bias", vp), ("pro", i32), ("act", i32),
                 ("x_in", vp), ("ld_x", i64), ("g1", vp), ("b1", vp), ("g2", vp), ("b2", vp),
                 ("ids", vp), ("id_stride", i64), ("table", vp), ("pos_row", vp),
@@ -108,6 +121,7 @@ class DecodeGemvDesc(C.Structure):
 
 
 class DecodeLinearDesc(C.Structure):
+    _c_name_ = "vct_decode_linear_desc"
     _fields_ = [("M", i32), ("N", i32), ("K", i32), ("out_dtype", i32), ("act", i32), ("res_dtype", i32),
                 ("x", vp), ("ldx", i64), ("x_pre", vp), ("ld_pre", i64), ("ln_g", vp), ("ln_b", vp), ("x_norm", vp), ("ld_norm", i64),
                 ("W", vp), ("ldw", i64), ("bias", vp), ("res", vp), ("ld_res", i64), ("out", vp), ("ldo", i64),
@@ -115,6 +129,7 @@ class DecodeLinearDesc(C.Structure):
 
 
 class DecodeBlockDesc(C.Structure):
+    _c_name_ = "vct_decode_block_desc"
     _fields_ = [("kind", i32), ("d", i32), ("ff", i32), ("V", i32), ("Lk", i32), ("act", i32),
                 ("id", vp), ("table", vp), ("pos_row", vp), ("res", vp), ("res_bias", vp), ("part", vp), ("n_part", i32), ("pad0", i32),
                 ("g1", vp), ("b1", vp), ("g2", vp), ("b2", vp), ("x_out", vp), ("w_a", vp), ("ld_a", i64), ("b_a", vp), ("slot", vp),
@@ -127,6 +142,7 @@ MM_MAX_MODAL = 8
 
 class MmFrontendDesc(C.Structure):
     """include/vct_hip.h, vct_mm_frontend_desc: the multi-modal encoder front end."""
+    _c_name_ = "vct_mm_frontend_desc"
     _fields_ = [("dtype", i32), ("n", i32), ("B", i32), ("d", i32), ("n_labels", i32), ("reserved", i32),
                 ("T", i32 * MM_MAX_MODAL), ("u", vp * MM_MAX_MODAL), ("mask", vp * MM_MAX_MODAL),
                 ("temp", vp), ("modal_w", vp), ("labels", vp), ("x0", vp), ("key_pad", vp), ("dx", vp),
@@ -139,6 +155,7 @@ TEMPORAL = {"encoding": 0, "embedding": 1}
 
 class EncFrontendExDesc(C.Structure):
     """include/vct_hip.h, vct_enc_frontend_ex_desc: the encoder front end with every `mme` option."""
+    _c_name_ = "vct_enc_frontend_ex_desc"
     _fields_ = [("dtype", i32), ("n", i32), ("B", i32), ("d", i32), ("n_labels", i32), ("agg", i32), ("temporal", i32), ("norm", i32),
                 ("emb_rows", i32), ("site", u32), ("p_drop", f32), ("reserved", i32),
                 ("T", i32 * MM_MAX_MODAL), ("u", vp * MM_MAX_MODAL), ("mask", vp * MM_MAX_MODAL),
@@ -149,6 +166,7 @@ class EncFrontendExDesc(C.Structure):
 
 class HmmMixDesc(C.Structure):
     """include/vct_hip.h, vct_hmm_mix_desc: row routing between the layers of the hierarchical encoder."""
+    _c_name_ = "vct_hmm_mix_desc"
     _fields_ = [("dtype", i32), ("B", i32), ("S", i32), ("d", i32), ("init", i32), ("reserved", i32),
                 ("take", vp), ("y", vp), ("x0", vp), ("x", vp), ("dx", vp), ("dy", vp), ("acc", vp), ("dx0", vp)]
 
@@ -159,6 +177,7 @@ MATCH_TEMP = {"none": 0, "exp": 1, "div": 2}
 
 class MatchLossDesc(C.Structure):
     """include/vct_hip.h, vct_match_loss_desc: the contrastive video-text loss, forward and backward."""
+    _c_name_ = "vct_match_loss_desc"
     _fields_ = [("B", i32), ("Dt", i32), ("loss_kind", i32), ("temp_kind", i32), ("text", vp), ("ld_text", i64), ("vid", vp), ("ld_vid", i64),
                 ("temp", vp), ("loss", vp), ("dvid", vp), ("ld_dvid", i64), ("dtemp", vp), ("sim", vp), ("ld_sim", i64),
                 ("workspace", vp), ("workspace_bytes", i64)]
@@ -166,6 +185,7 @@ class MatchLossDesc(C.Structure):
 
 class MatchAggDesc(C.Structure):
     """include/vct_hip.h, vct_match_agg_desc: the aggregation row of every sample <-> the matching head."""
+    _c_name_ = "vct_match_agg_desc"
     _fields_ = [("dtype", i32), ("B", i32), ("Te", i32), ("d", i32), ("empty", i32), ("beta", f32), ("mem", vp), ("agg", vp),
                 ("dagg", vp), ("dmem", vp)]
 
@@ -176,6 +196,7 @@ RETRIEVAL_PHASE = {"prep": 1, "stats": 2, "gt": 4, "count": 8, "finish": 16}
 
 class RetrievalDesc(C.Structure):
     """include/vct_hip.h, vct_retrieval_desc: text->video / video->text ranks and their statistics over a whole split."""
+    _c_name_ = "vct_retrieval_desc"
     _fields_ = [("Nt", i32), ("Nv", i32), ("Dt", i32), ("mode", i32), ("text", vp), ("ld_text", i64), ("vid", vp), ("ld_vid", i64),
                 ("gt", vp), ("tau", vp), ("ranks_t2v", vp), ("ranks_v2t", vp), ("out", vp), ("workspace", vp), ("workspace_bytes", i64),
                 ("phases", i32), ("reserved", i32)]
@@ -183,11 +204,13 @@ class RetrievalDesc(C.Structure):
 
 class SampleCtl(C.Structure):
     """include/vct_hip.h, vct_sample_ctl: the settings vct_sample_select reads from device memory."""
+    _c_name_ = "vct_sample_ctl"
     _fields_ = [("seed", u32), ("top_k", i32), ("inv_temp", f32), ("top_p", f32)]
 
 
 class SampleSelectDesc(C.Structure):
     """include/vct_hip.h, vct_sample_select_desc: one sampled selection step."""
+    _c_name_ = "vct_sample_select_desc"
     _fields_ = [("dtype", i32), ("rows", i32), ("V", i32), ("t", i32), ("x", vp), ("ldx", i64), ("out", vp), ("out_stride", i64),
                 ("end_id", i64), ("pad_id", i64), ("ended", vp), ("ended_count", vp), ("all_ended_at", vp), ("step_logp", vp),
                 ("seq_logp", vp), ("ctl", vp), ("workspace", vp), ("workspace_bytes", i64)]
@@ -198,6 +221,7 @@ CIDER_MAX_LEN, CIDER_MAX_ORDER = 64, 4
 
 class CiderDesc(C.Structure):
     """include/vct_hip.h, vct_cider_desc: CIDEr-D of sampled ids against device-resident reference tables."""
+    _c_name_ = "vct_cider_desc"
     _fields_ = [("B", i32), ("N", i32), ("L", i32), ("n", i32), ("ids", vp), ("stride_b", i64), ("stride_n", i64), ("stride_l", i64),
                 ("end_id", i64), ("log_nvid", f64), ("two_sigma_sq", f64), ("vid_rows", vp), ("n_videos", i32), ("table_cap", i32),
                 ("table_keys", vp), ("table_idf", vp), ("vid_ref_ptr", vp), ("ref_len", vp), ("ref_norm", vp), ("ref_ent_ptr", vp),
@@ -209,12 +233,30 @@ CAPMETRIC_COUNT_COLS = 12
 
 class CapMetricDesc(C.Structure):
     """include/vct_hip.h, vct_capmetric_desc: per-caption BLEU / ROUGE-L statistics of decoded ids against reference token lists."""
+    _c_name_ = "vct_capmetric_desc"
     _fields_ = [("C", i32), ("L", i32), ("ids", vp), ("stride_c", i64), ("stride_l", i64), ("end_id", i64), ("vid_rows", vp),
                 ("n_videos", i32), ("reserved", i32), ("beta_sq", f64), ("vid_ref_ptr", vp), ("ref_tok_ptr", vp), ("ref_tok", vp),
                 ("counts", vp), ("rouge", vp)]
 
 
 DEC_PRO = {"none": 0, "embed": 1, "ln": 2, "ln_ln": 3, "self_attn": 4, "cross_attn": 5}
+
+
+def _c(prefix, table):
+    return {prefix + k.upper(): v for k, v in table.items() if k is not None}
+
+
+# the C spelling of every constant above that mirrors an enum / macro of include/vct_hip.h (tests/test_abi_cpu.py prints them from C)
+C_CONSTANTS = {
+    "VCT_F32": F32, "VCT_BF16": BF16, "VCT_ABI_VERSION": ABI_VERSION, "VCT_GEMM_GROUP_MAX": GEMM_GROUP_MAX,
+    "VCT_GEMM_ROUTE_INTS": GEMM_ROUTE_INTS, "VCT_MM_MAX_MODAL": MM_MAX_MODAL, "VCT_CIDER_MAX_LEN": CIDER_MAX_LEN,
+    "VCT_CIDER_MAX_ORDER": CIDER_MAX_ORDER, "VCT_CAPMETRIC_COUNT_COLS": CAPMETRIC_COUNT_COLS,
+    **_c("VCT_ACT_", ACT), **{text.split()[0]: code for code, text in _ERR.items()},
+    "VCT_AGG_MEAN": AGG["avg"], "VCT_AGG_MAX": AGG["max"],
+    "VCT_TEMPORAL_FIXED": TEMPORAL["encoding"], "VCT_TEMPORAL_LEARNED": TEMPORAL["embedding"],
+    **_c("VCT_MATCH_", MATCH_LOSS), **_c("VCT_MATCH_TEMP_", MATCH_TEMP), **_c("VCT_RETRIEVAL_", RETRIEVAL_MODE),
+    **_c("VCT_RETRIEVAL_PH_", RETRIEVAL_PHASE), **_c("VCT_DEC_PRO_", DEC_PRO),
+}
 
 _SIGS = {
     "vct_abi_version": (C.c_int, []),
@@ -320,7 +362,6 @@ _SIGS = {
     "vct_tap": (C.c_int, [C.c_int, C.c_int, vp]),
     "vct_tap_collect": (C.c_int, [C.c_int, C.POINTER(f32), C.c_int]),
 }
-_OPTIONAL = {}
 HOST_FN = C.CFUNCTYPE(C.c_int, vp)        # int fn(void* arg): vct_cmdlist_host_call
 
 _lib = None
@@ -328,7 +369,20 @@ _lib = None
 
 def exported_symbols():
     """Every symbol include/vct_hip.h declares (used by the CPU-side ABI test)."""
-    return sorted(list(_SIGS) + list(_OPTIONAL))
+    return sorted(_SIGS)
+
+
+def _bind(lib, where=None):
+    """Give every entry point of `lib` its _SIGS types and check its ABI version.  where: None for the in-tree library, else how
+    the developer's A/B library was named (it leads the messages)."""
+    for name, (res, args) in _SIGS.items():
+        if not hasattr(lib, name):
+            raise RuntimeError(f"{where or LIB_PATH}: symbol {name} is missing (built from another include/vct_hip.h)")
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = res, args
+    if lib.vct_abi_version() != ABI_VERSION:
+        raise RuntimeError(f"{where}: ABI version {lib.vct_abi_version()} != {ABI_VERSION}" if where else "libvct_hip.so ABI version mismatch")
+    return lib
 
 
 def load():
@@ -338,31 +392,14 @@ def load():
     if _AB_LIB:
         # developer A/B library (tools/ab_build.sh): no stamp (it is built from an older header on purpose), but the same ABI gate as
         # the in-tree library -- a .so with another entry-point table must not be driven through this ctypes table
-        lib = C.CDLL(_AB_LIB)
-        for name, (res, args) in _SIGS.items():
-            if not hasattr(lib, name):
-                raise RuntimeError(f"VCT_LIB_PATH={_AB_LIB}: symbol {name} is missing (built from another include/vct_hip.h)")
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-        if lib.vct_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"VCT_LIB_PATH={_AB_LIB}: ABI version {lib.vct_abi_version()} != {ABI_VERSION}")
-        _lib = lib
-        return lib
+        _lib = _bind(C.CDLL(_AB_LIB), f"VCT_LIB_PATH={_AB_LIB}")
+        return _lib
     _ensure_current()
     if not os.path.exists(LIB_PATH):
         raise RuntimeError(
             f"{LIB_PATH} is missing: the HIP extension is the product path and has no CPU/eager fallback. "
             "Build it with `python -c 'import __graft_entry__ as g; g.build()'`.")
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGS.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
-    for name, (res, args) in _OPTIONAL.items():
-        if hasattr(lib, name):
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
-    if lib.vct_abi_version() != ABI_VERSION:
-        raise RuntimeError("libvct_hip.so ABI version mismatch")
+    lib = _bind(C.CDLL(LIB_PATH))
     # one HIP runtime per process: our kernels must launch on torch's streams
     try:
         n = sum(1 for ln in open("/proc/self/maps") if "libamdhip64" in ln and " r-xp " in ln)

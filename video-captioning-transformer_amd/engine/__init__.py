@@ -4,7 +4,7 @@ The reference runs this path as ~60 stock torch.nn calls under autograd (model/M
 model/CapDecoder.py:34-60, torch nn/modules/transformer.py:951-982,1143-1199).  Here the graph is
 static and known, so forward and backward are explicit kernel schedules over pre-allocated HBM
 buffers: no autograd tape, no temporaries, no host synchronisation -- the whole step is
-hipGraph-capturable.  Every arithmetic step is a libvct_hip.so kernel (ops.py); torch is used for
+hipGraph-capturable.  Every arithmetic step is a libvct_hip.so kernel (the ops package); torch is used for
 memory, streams and a few boolean mask preparations only.
 
 Data layout in HBM (row-major, tokens x features):
