@@ -108,9 +108,11 @@ def _presum(x, res, mask):
     return xm + r, xm.abs() + r.abs(), 2 * U24 * (xm.abs() + r.abs())
 
 
-def ln_fwd(x, res, gamma, beta, mask=None):
-    """dict(y, mean, rstd, e_y, e_mean, e_rstd): references and the error terms e of the module docstring (u_out |ref| not included)."""
-    s, _, es = _presum(x, res, mask)
+def ln_fwd(x, res, gamma, beta, mask=None, es=None):
+    """dict(y, mean, rstd, e_y, e_mean, e_rstd): references and the error terms e of the module docstring (u_out |ref| not included).
+    es: the error of the norm's input s where it is not the one product and one sum of _presum (tests/frontend_ref.py)."""
+    s, _, es0 = _presum(x, res, mask)
+    es = es0 if es is None else es.to(s.device)
     g, b = gamma.to(F64).to(s.device), beta.to(F64).to(s.device)
     d = s.shape[1]
     mean = s.mean(1)
@@ -128,9 +130,10 @@ def ln_fwd(x, res, gamma, beta, mask=None):
     return dict(y=y, mean=mean, rstd=rstd, e_y=e_y, e_mean=e_mean, e_rstd=rstd * e_r)
 
 
-def ln_bwd(dy, x, res, gamma, mean, rstd, mask=None, dy_err=None):
-    """dict(ds, dxo, dgamma, dbeta, e_ds, e_dxo, e_dgamma, e_dbeta).  mean / rstd: the saved statistics (exact operands)."""
-    s, _, es = _presum(x, res, mask)
+def ln_bwd(dy, x, res, gamma, mean, rstd, mask=None, dy_err=None, es=None):
+    """dict(ds, dxo, dgamma, dbeta, e_ds, e_dxo, e_dgamma, e_dbeta).  mean / rstd: the saved statistics (exact operands); es as in ln_fwd."""
+    s, _, es0 = _presum(x, res, mask)
+    es = es0 if es is None else es.to(s.device)
     dev = s.device
     M, d = s.shape
     g, dy = gamma.to(F64).to(dev), dy.to(F64).to(dev)

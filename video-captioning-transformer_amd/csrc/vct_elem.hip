@@ -470,6 +470,11 @@ __global__ void sce_finalize_kernel(int N, float alpha, const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
+// a same-type cast is a copy of the bits (bf16 -> fp32 -> bf16 through the hardware conversion would quiet a signalling NaN)
+template <typename TS, typename TD> __device__ __forceinline__ TD cast_one(TS v) {
+  if constexpr (std::is_same<TS, TD>::value) return v;
+  else return from_f<TD>(to_f<TS>(v));
+}
 template <typename TS, typename TD>
 __global__ void cast_kernel(const TS* __restrict__ src, TD* __restrict__ dst, int64_t n) {
   const int64_t n4 = n / 4;
@@ -477,12 +482,12 @@ __global__ void cast_kernel(const TS* __restrict__ src, TD* __restrict__ dst, in
     const PackT<TS, 4> s = reinterpret_cast<const PackT<TS, 4>*>(src)[i];
     PackT<TD, 4> o;
 #pragma unroll
-    for (int j = 0; j < 4; j++) o.v[j] = from_f<TD>(to_f<TS>(s.v[j]));
+    for (int j = 0; j < 4; j++) o.v[j] = cast_one<TS, TD>(s.v[j]);
     reinterpret_cast<PackT<TD, 4>*>(dst)[i] = o;
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
     const int64_t i = n4 * 4 + threadIdx.x;
-    dst[i] = from_f<TD>(to_f<TS>(src[i]));
+    dst[i] = cast_one<TS, TD>(src[i]);
   }
 }
 
@@ -499,17 +504,27 @@ __global__ __launch_bounds__(256) void gather_pad_rows_kernel(const float* __res
   const int64_t clip = idx[b], r0 = offsets[clip], len = offsets[clip + 1] - r0;
   const bool valid = t < len;
   if (lane == 0) mask[row] = valid ? 0 : 1;
-  const float* src = store + (size_t)(r0 + (valid ? t : 0)) * E;
   TD* dst = out + (size_t)row * E;
   const int e4 = (E % 4 == 0) ? E / 4 : 0;     // rows are 16-byte aligned only then
+  if (!valid) {
+    // a padded row reads nothing from the store (valid is wave-uniform: one wave owns the row).  The first row of a clip of length 0
+    // that ends the store lies one row past its end.
+    PackT<TD, 4> z;
+#pragma unroll
+    for (int j = 0; j < 4; j++) z.v[j] = from_f<TD>(0.0f);
+    for (int i = lane; i < e4; i += 64) reinterpret_cast<PackT<TD, 4>*>(dst)[i] = z;
+    for (int i = e4 * 4 + lane; i < E; i += 64) dst[i] = from_f<TD>(0.0f);
+    return;
+  }
+  const float* src = store + (size_t)(r0 + t) * E;
   for (int i = lane; i < e4; i += 64) {
-    PackT<float, 4> v = reinterpret_cast<const PackT<float, 4>*>(src)[i];    // unconditional load, zeroed after
+    const PackT<float, 4> v = reinterpret_cast<const PackT<float, 4>*>(src)[i];
     PackT<TD, 4> o;
 #pragma unroll
-    for (int j = 0; j < 4; j++) o.v[j] = from_f<TD>(valid ? v.v[j] : 0.0f);
+    for (int j = 0; j < 4; j++) o.v[j] = from_f<TD>(v.v[j]);
     reinterpret_cast<PackT<TD, 4>*>(dst)[i] = o;
   }
-  for (int i = e4 * 4 + lane; i < E; i += 64) dst[i] = from_f<TD>(valid ? src[i] : 0.0f);
+  for (int i = e4 * 4 + lane; i < E; i += 64) dst[i] = from_f<TD>(src[i]);
 }
 
 constexpr int AMX_THREADS = 1024;
