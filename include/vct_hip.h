@@ -494,6 +494,40 @@ int vct_embed_fwd(int dtype, int B, int S, int d, const int64_t* ids, int64_t id
 int vct_preln_fwd(int out_dtype, int M, int d, const float* x, const float* gamma, const float* beta, void* y, void* stream);
 int vct_text_pool(int out_dtype, int B, int L, int Lids, int d, const int64_t* ids, int64_t ld_ids, const float* x,
                   const float* gamma, const float* beta, void* y, int32_t* eot, int32_t* err, void* stream);
+/* ---------------------------------------------------------------------------------------------
+ * The frozen CLIP vision tower (vision.py): the three kernels around the pre-LN block, which is vct_preln_fwd, vct_gemm
+ * and vct_attn_fwd as in the text tower.  Forward only.
+ * vct_frames_to_patches: uint8 RGB frames [N, H, W, 3] -> the patch-embedding GEMM's A operand,
+ *     out[(n * G + gy) * G + gx, c * P * P + py * P + px],  G = R / P,  in out_dtype (VCT_F32 | VCT_BF16): the row layout of
+ *   conv1.weight.view(width, 3 * P * P).  The image is PIL's integer bicubic resize (shorter side to R, the longer to
+ *   int(R * long / short)), centre-cropped to R x R: horizontal pass first, the vertical pass on its uint8 result, int32 accumulators
+ *   that start at 2^21, are shifted right by 22 and clamped to 0 .. 255.  The HOST decides every window and weight: hx_min / hx_len
+ *   [R] and hx_w [R, kx] (int32, 22-bit fixed point, zero-padded) describe the R cropped columns of the horizontal pass in input
+ *   columns, vy_* [R] / [R, ky] the R cropped rows of the vertical pass in input rows; a pass PIL skips (the size does not change) is
+ *   the one-tap table of weight 2^22.  lut: [3][256] in out_dtype, the value of every byte per channel (ToTensor + Normalize as the
+ *   host computed it); the kernel only looks it up, so every output element is one of the table's.  stage_rows: the largest number of
+ *   input rows the P rows of one patch read (max over gy of vy_min[gy P + P - 1] + vy_len[gy P + P - 1] - vy_min[gy P]); the
+ *   horizontal pass of those rows is staged in LDS as uint8.  crop (NULL: not written): the cropped image, uint8 [N, R, R, 3].
+ *   One launch for any N, one workgroup per (frame, patch); windows are clamped to the frame and to stage_rows on the device.
+ *   replaces: clip's `_transform` (Resize(BICUBIC), CenterCrop, ToTensor, Normalize on a PIL image) and the unfold of `conv1` in
+ *   VisionTransformer.forward (clip/model.py), as reached from the reference's predict_video.py --video.
+ *   NULL operand / bad dtype: VCT_E_ARG; N, H, W, R, P, kx, ky, stage_rows < 1, R % P, kx > W, ky or stage_rows > H, N * G * G or
+ *   3 * H * W beyond int32, or tables + staging + one patch (4 P (kx + ky + 4) + 3 P stage_rows + 3 P P bytes) over 64 KB of LDS:
+ *   VCT_E_SHAPE; P not a multiple of 8, out not 16-byte, a table, an fp32 lut or crop not 4-byte aligned: VCT_E_ALIGN.
+ * vct_vit_embed: s[n, 0] = cls + pos[0], s[n, 1 + g] = e[n * (L - 1) + g] + pos[1 + g]; x[n * L + l] = LayerNorm(s[n, l]) (gamma /
+ *   beta = ln_pre, eps 1e-5).  e: fp32 [N * (L - 1), d], the patch GEMM's output; x: the fp32 residual stream [N * L, d].
+ *   replaces: the class-token concatenation, `+ positional_embedding` and `ln_pre` of VisionTransformer.forward.
+ * vct_vit_pool: y[n] = LayerNorm(x[n * L]) in out_dtype (gamma / beta = ln_post): the class rows only; no other row is read.
+ *   replaces: `ln_post(x[:, 0, :])` in front of `@ proj`.
+ * Both: d a multiple of 4 (VCT_E_ALIGN) up to 1024 (VCT_E_SHAPE); N >= 1, L >= 2 (embed) / 1 (pool) (VCT_E_SHAPE); every fp32 operand
+ * 16-byte, a bf16 y 8-byte aligned (VCT_E_ALIGN); NULL operand / bad dtype: VCT_E_ARG.  All before any device use.
+ * --------------------------------------------------------------------------------------------- */
+int vct_frames_to_patches(int out_dtype, int N, int H, int W, int R, int P, const uint8_t* frames, const int32_t* hx_min,
+                          const int32_t* hx_len, const int32_t* hx_w, int kx, const int32_t* vy_min, const int32_t* vy_len,
+                          const int32_t* vy_w, int ky, int stage_rows, const void* lut, void* out, uint8_t* crop, void* stream);
+int vct_vit_embed(int N, int L, int d, const float* e, const float* cls, const float* pos, const float* gamma, const float* beta,
+                  float* x, void* stream);
+int vct_vit_pool(int out_dtype, int N, int L, int d, const float* x, const float* gamma, const float* beta, void* y, void* stream);
 
 int vct_embed_bwd(int dtype, int B, int S, int d, int V, const int64_t* ids, int64_t id_batch_stride,
                   int64_t pad_id, const void* dx, float* dtable, int32_t* id_ws, int64_t id_ws_ints, int incremental,

@@ -6,59 +6,11 @@
 //   vct_text_pool : per caption the FIRST index of the largest id (CLIP's `text.argmax(dim=-1)`: the EOT token has the largest id),
 //                   that row of the stream through ln_final, in the compute dtype.
 // Both: one wave per row, the row in registers (float4 loads, <= 16 values per lane => d <= 1024), two-pass variance in fp32 -- the
-// scheme of vct_norm.hip.  HBM-bound; nothing is staged in LDS.
+// scheme of vct_norm.hip (vct_ln_row.h, shared with the vision tower).  HBM-bound; nothing is staged in LDS.
 #include "vct_common.h"
+#include "vct_ln_row.h"
 
 namespace vct {
-
-constexpr int TXT_MAXIT = 4;   // 4 x 64 lanes x float4 = 1024 columns
-
-template <typename T> struct alignas(sizeof(T) * 4) Out4 { T v[4]; };
-
-// normalises the row `src` (d columns, fp32) into `dst`; every lane of the wave takes part
-template <typename T>
-__device__ __forceinline__ void ln_row(const float* __restrict__ src, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                       T* __restrict__ dst, int d, int lane) {
-  const int nvec = d >> 2;
-  float s[TXT_MAXIT][4];
-  float sum = 0.0f;
-#pragma unroll
-  for (int it = 0; it < TXT_MAXIT; it++) {
-    const int vi = it * 64 + lane;
-    if (vi < nvec) {
-      const float4 v = *reinterpret_cast<const float4*>(src + vi * 4);
-      s[it][0] = v.x; s[it][1] = v.y; s[it][2] = v.z; s[it][3] = v.w;
-      sum += (v.x + v.y) + (v.z + v.w);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; j++) s[it][j] = 0.0f;
-    }
-  }
-  const float mean = wave_sum(sum) / (float)d;
-  float sq = 0.0f;
-#pragma unroll
-  for (int it = 0; it < TXT_MAXIT; it++) {
-    if (it * 64 + lane < nvec) {
-#pragma unroll
-      for (int j = 0; j < 4; j++) { const float c = s[it][j] - mean; sq += c * c; }
-    }
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)d + 1e-5f);
-#pragma unroll
-  for (int it = 0; it < TXT_MAXIT; it++) {
-    const int vi = it * 64 + lane;
-    if (vi < nvec) {
-      const float4 g = *reinterpret_cast<const float4*>(gamma + vi * 4);
-      const float4 b = *reinterpret_cast<const float4*>(beta + vi * 4);
-      Out4<T> o;
-      o.v[0] = from_f<T>((s[it][0] - mean) * rstd * g.x + b.x);
-      o.v[1] = from_f<T>((s[it][1] - mean) * rstd * g.y + b.y);
-      o.v[2] = from_f<T>((s[it][2] - mean) * rstd * g.z + b.z);
-      o.v[3] = from_f<T>((s[it][3] - mean) * rstd * g.w + b.w);
-      *reinterpret_cast<Out4<T>*>(dst + vi * 4) = o;
-    }
-  }
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void preln_fwd_kernel(int M, int d, const float* __restrict__ x, const float* __restrict__ gamma,
@@ -109,21 +61,13 @@ __global__ __launch_bounds__(256) void text_pool_kernel(int B, int L, int Lids, 
   ln_row<T>(x + ((size_t)b * L + at) * d, gamma, beta, dst, d, lane);
 }
 
-static int text_ln_check(int out_dtype, int d) {
-  if (out_dtype != VCT_F32 && out_dtype != VCT_BF16) return VCT_E_ARG;
-  if (d <= 0) return VCT_E_SHAPE;
-  if (d % 4) return VCT_E_ALIGN;
-  if (d > 1024) return VCT_E_SHAPE;
-  return VCT_OK;
-}
-
 }  // namespace vct
 
 using namespace vct;
 
 extern "C" int vct_preln_fwd(int out_dtype, int M, int d, const float* x, const float* gamma, const float* beta, void* y, void* stream) {
   if (!x || !gamma || !beta || !y) return VCT_E_ARG;
-  const int rc = text_ln_check(out_dtype, d);
+  const int rc = ln_row_check(out_dtype, d);
   if (rc) return rc;
   if (M <= 0) return VCT_E_SHAPE;
   if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) return VCT_E_ALIGN;
@@ -140,7 +84,7 @@ extern "C" int vct_preln_fwd(int out_dtype, int M, int d, const float* x, const 
 extern "C" int vct_text_pool(int out_dtype, int B, int L, int Lids, int d, const int64_t* ids, int64_t ld_ids, const float* x,
                              const float* gamma, const float* beta, void* y, int32_t* eot, int32_t* err, void* stream) {
   if (!ids || !x || !gamma || !beta || !y || !eot || !err) return VCT_E_ARG;
-  const int rc = text_ln_check(out_dtype, d);
+  const int rc = ln_row_check(out_dtype, d);
   if (rc) return rc;
   if (B <= 0 || L <= 0 || Lids < L || ld_ids < Lids) return VCT_E_SHAPE;
   if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta) & 15) return VCT_E_ALIGN;

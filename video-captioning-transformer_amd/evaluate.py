@@ -70,6 +70,42 @@ def v2t_batch(model, video_feats: Sequence[torch.Tensor], video_masks: Optional[
 
 
 @torch.no_grad()
+def v2t_frames(model, tower, videos: Sequence[torch.Tensor], max_len: int = 30, beam_size: Optional[int] = None,
+               return_attn: bool = False, sample: Optional[dict] = None, extra_feats: Optional[Sequence[torch.Tensor]] = None,
+               extra_masks: Optional[Sequence[torch.Tensor]] = None):
+    """predict_video.py --video, batched: videos = list of uint8 [T_i, H_i, W_i, 3] RGB frames (lengths and sizes may differ), tower =
+    a vision.ClipVisionTower.  Each video is encoded on the device into its rows of ONE padded [B, max T_i, dim] matrix (padding
+    rows zero, mask True there) and that goes to v2t_batch with its keywords: no feature visits the host.  A model with more than
+    one feature stream takes the other streams' precomputed features as extra_feats (list of [B, T, E], in modal order behind the
+    first) with extra_masks (list of bool [B, T], or None when nothing is padded)."""
+    _check_sample(sample, beam_size, return_attn)
+    shapes = list(model.model_config["modal_shape"])
+    if tower.dim != shapes[0]:
+        raise ValueError(f"v2t_frames: the tower yields {tower.dim} features per frame, the model's first modal_shape entry is {shapes[0]}")
+    extra_feats = list(extra_feats) if extra_feats is not None else []
+    if len(extra_feats) != len(shapes) - 1:
+        raise ValueError(f"v2t_frames: the model has {len(shapes)} feature streams; extra_feats must hold the other {len(shapes) - 1}, "
+                         f"got {len(extra_feats)}")
+    if len(videos) < 1 or any(not torch.is_tensor(v) or v.dim() != 4 or v.shape[0] < 1 for v in videos):
+        raise ValueError("v2t_frames: videos is a non-empty list of uint8 [T, H, W, 3] tensors with T >= 1")
+    if extra_masks is not None and len(extra_masks) != len(extra_feats):
+        raise ValueError("v2t_frames: extra_masks must pair with extra_feats")
+    dev = tower.device
+    B, T = len(videos), max(v.shape[0] for v in videos)
+    feats = torch.zeros(B, T, tower.dim, dtype=torch.float32, device=dev)
+    lengths = torch.tensor([v.shape[0] for v in videos])
+    for b, v in enumerate(videos):
+        tower.encode_frames(v, out=feats[b, :v.shape[0]])
+    mask = (torch.arange(T)[None, :] >= lengths[:, None]).to(dev, non_blocking=True)
+    ragged = bool((lengths != T).any())
+    masks = None
+    if ragged or extra_masks is not None:
+        others = list(extra_masks) if extra_masks is not None else [torch.zeros(f.shape[:2], dtype=torch.bool) for f in extra_feats]
+        masks = [mask] + others
+    return v2t_batch(model, [feats] + extra_feats, masks, max_len=max_len, beam_size=beam_size, return_attn=return_attn, sample=sample)
+
+
+@torch.no_grad()
 def v2t_single(model, video_feat: Sequence[torch.Tensor], max_len: int = 30, beam_size: Optional[int] = None,
                return_attn: bool = False, sample: Optional[dict] = None):
     """train.py:194-203: one video (list of [T, E] per modality), no mask.  return_attn: (caption, maps fp32 [layers, steps, Te]).

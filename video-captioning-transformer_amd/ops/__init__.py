@@ -23,3 +23,4 @@ from .optim import adam_bump, adam_ranges_table, adam_step, adam_step_2d, adam_s
 from .runtime import (TAPS, LaunchList, host_call, is_recording, masked_stream, stream_wait, sync_record, sync_wait, tap,
                       tap_collect, taps_enable)
 from .scoring import capmetric_counts, capmetric_finish, check_capmetric_ids, check_cider_ids, cider_d, cider_d_eval, scst_advantages
+from .vision import frames_to_patches, vit_embed, vit_pool

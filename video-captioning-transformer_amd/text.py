@@ -12,7 +12,7 @@ from a host tokenizer, so L is a host decision; L > 64 (the attention kernel's l
 Schedule, seven launches per layer and three around them:
     vct_embed_fwd (fp32 stream) | vct_preln_fwd, vct_gemm [3W, W] + bias, vct_attn_fwd causal, vct_gemm out_proj + bias + stream -> fp32,
     vct_preln_fwd, vct_gemm c_fc + bias + QuickGELU, vct_gemm c_proj + bias + stream -> fp32 | vct_text_pool, vct_gemm projection -> fp32
-The residual stream is fp32 in both modes; the GEMM operands are bf16 (rounded once, at load) or fp32 (parity mode).  Everything is
+The per-layer launches are run_layers, which the vision tower (vision.py) shares.  The residual stream is fp32 in both modes; the GEMM operands are bf16 (rounded once, at load) or fp32 (parity mode).  Everything is
 enqueued on the current stream through the runtime's launch wrapper; nothing synchronises.  The weights are no part of any
 state_dict (the reference's TextEncoder is not a module either).  No tokenizer is shipped: CLIP's BPE merges are a download -- pass
 `tokenize=clip.tokenize` (or an equivalent strings -> int [B, 77] callable), or pass ids."""
@@ -158,8 +158,30 @@ def trim_length(ids: torch.Tensor) -> int:
     return L
 
 
+def run_layers(lws, xa, xb, h, qkv, o, f, B, H, L, causal, kept=None):
+    """CLIP's pre-LN ResidualAttentionBlock over the fp32 stream xa [B * L, W], seven launches per layer; the result is in xa again.
+    xb: the second stream buffer; h, qkv, o, f: compute-dtype scratch [B * L, W | 3 W | W | ff].  kept: a list that receives clones of
+    every stored intermediate, one dict per layer.  Shared by the text tower (causal) and the vision tower (vision.py; not causal)."""
+    W = xa.shape[1]
+    for lw in lws:
+        ops.preln_fwd(xa, lw["ln1_g"], lw["ln1_b"], h)
+        if kept is not None:
+            k = {"h1": h.clone()}
+        ops.gemm(h, lw["w_qkv"], qkv, bias=lw["b_qkv"])
+        ops.attn_fwd(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], o, B, H, L, L, causal=causal)
+        ops.gemm(o, lw["w_o"], xb, bias=lw["b_o"], addend=xa)
+        ops.preln_fwd(xb, lw["ln2_g"], lw["ln2_b"], h)
+        if kept is not None:
+            k.update(qkv=qkv.clone(), o=o.clone(), x1=xb.clone(), h2=h.clone())
+        ops.gemm(h, lw["w_fc"], f, bias=lw["b_fc"], act="quick_gelu")
+        ops.gemm(f, lw["w_proj"], xa, bias=lw["b_proj"], addend=xb)
+        if kept is not None:
+            k.update(f=f.clone(), x2=xa.clone())
+            kept.append(k)
+
+
 class ClipTextTower:
-    """See the module docstring.  `dim` = P is what Matching / TextEncoder.dim must equal."""
+    """See the module docstring. `dim` = P is what Matching / TextEncoder.dim must equal."""
 
     def __init__(self, weights: dict, device, compute_dtype=torch.bfloat16, tokenize: Optional[Callable] = None,
                  heads: Optional[int] = None):
@@ -249,26 +271,11 @@ class ClipTextTower:
             raise ValueError(f"CLIP text tower: out must be fp32 [{B}, {self.dim}] on {self.device}")
         b = self._buffers(B, L)
         xa, xb, h, qkv, o, f = b["xa"], b["xb"], b["h"], b["qkv"], b["o"], b["f"]
-        W, H = self.width, self.heads
         kept = {"ids": ids_dev.clone(), "L": L, "layers": []} if keep else None
         ops.embed_fwd(ids_dev, L, self.tok, self.pos, xa)
         if keep:
             kept["x0"] = xa.clone()
-        for lw in self.lw:
-            ops.preln_fwd(xa, lw["ln1_g"], lw["ln1_b"], h)
-            if keep:
-                k = {"h1": h.clone()}
-            ops.gemm(h, lw["w_qkv"], qkv, bias=lw["b_qkv"])
-            ops.attn_fwd(qkv[:, :W], qkv[:, W:2 * W], qkv[:, 2 * W:], o, B, H, L, L, causal=True)
-            ops.gemm(o, lw["w_o"], xb, bias=lw["b_o"], addend=xa)
-            ops.preln_fwd(xb, lw["ln2_g"], lw["ln2_b"], h)
-            if keep:
-                k.update(qkv=qkv.clone(), o=o.clone(), x1=xb.clone(), h2=h.clone())
-            ops.gemm(h, lw["w_fc"], f, bias=lw["b_fc"], act="quick_gelu")
-            ops.gemm(f, lw["w_proj"], xa, bias=lw["b_proj"], addend=xb)
-            if keep:
-                k.update(f=f.clone(), x2=xa.clone())
-                kept["layers"].append(k)
+        run_layers(self.lw, xa, xb, h, qkv, o, f, B, self.heads, L, True, kept["layers"] if keep else None)
         ops.text_pool(ids_dev, xa, L, self.lnf_g, self.lnf_b, b["pooled"], b["eot"], self.err)
         ops.gemm(b["pooled"], self.proj, out)
         if keep:
