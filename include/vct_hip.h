@@ -963,6 +963,57 @@ typedef struct vct_sample_select_desc {
 int64_t vct_sample_select_workspace_bytes(int dtype, int rows, int V);
 int vct_sample_select(const vct_sample_select_desc* d, void* stream);
 /* ---------------------------------------------------------------------------------------------
+ * Generation controls on the KV-cached decode step (csrc/vct_logit_controls.hip).  The reference has no logit rule of any kind;
+ * the semantics are the project's (decode.GenerationControls) and follow Hugging Face's logits processors of the same names.
+ *
+ * vct_logit_controls: edits the logits of step t IN PLACE, in their dtype, columns < V only, for `rows` rows, in front of the
+ * selection kernel of that step.  The settings are READ FROM DEVICE MEMORY (ctl, 160 bytes), so one captured graph serves every
+ * setting:
+ *   ctl = { int32 min_length; int32 ngram; float theta; float inv_theta; int32 n_banned; int32 reserved[3]; int32 banned[32] }
+ *   ngram is clamped to [0, 8] and n_banned to [0, 32] by the kernel; a banned id or history token outside [0, V) is ignored.
+ * History of row r: h[0 .. t-1].  parents == NULL: h[s] = ids[r * ids_stride + s] (the id matrix of a greedy / sampled session).
+ * parents != NULL (beams, rows = B*K, rows b*K .. b*K+K-1 = video b): ids is the token table and h follows the parent
+ * back-track as of step t: j = r; for s = t-1 .. 1: h[s] = ids[j * ids_stride + s], j = parents[s * parents_stride + j];
+ * h[0] = ids[j * ids_stride] (a parent outside its video's K rows is clamped into them).
+ * Per row with ended[r] == 0 (a row with ended[r] != 0 is not touched):
+ *   1. penalty  theta != 1: for every distinct token v of h that rule 2 does not ban, once: f = float(x[v]);
+ *               x[v] = round-to-nearest-even(f > 0 ? f * inv_theta : f * theta).
+ *   2. bans     x[v] = -inf for every banned[i], i < n_banned; for end_id while t <= min_length; and, with n = ngram >= 1 and
+ *               t >= n-1, for every h[j], n-1 <= j <= t-1, whose n-1 predecessors h[j-n+1 .. j-1] equal h[t-n+1 .. t-1].
+ * No element is written twice with different values.  One launch: a wave per row (four rows per workgroup), or with parents a
+ * workgroup per video and a wave per slot over the video's parent / token columns staged in LDS.  No atomics, no workspace; a
+ * second call on the same inputs is bit-identical.
+ * VCT_E_ARG: NULL descriptor / x / ids / ended / ctl, bad dtype; VCT_E_SHAPE: rows <= 0, V <= 0, ldx < V, t < 1, t > 64, and with
+ * parents K outside 1 .. 16 or rows not a multiple of K.  All before any device use.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct vct_logit_ctl {
+  int32_t min_length;
+  int32_t ngram;
+  float theta;
+  float inv_theta;
+  int32_t n_banned;
+  int32_t reserved[3];
+  int32_t banned[32];
+} vct_logit_ctl;
+
+typedef struct vct_logit_controls_desc {
+  int32_t dtype;              /* VCT_F32 / VCT_BF16: the logits */
+  int32_t rows, V, t;
+  void* x;                    /* [rows, ldx], edited in place */
+  int64_t ldx;
+  int64_t end_id;
+  const int64_t* ids;         /* id matrix, or the beams' token table */
+  int64_t ids_stride;
+  const uint8_t* ended;       /* [rows]: the session's ended / finished flags */
+  const int32_t* parents;     /* beams: [Lmax, rows] parent rows; NULL: histories are the rows of ids */
+  int64_t parents_stride;
+  int32_t K;                  /* beams per video (with parents) */
+  int32_t reserved;
+  const vct_logit_ctl* ctl;   /* device memory */
+} vct_logit_controls_desc;
+
+int vct_logit_controls(const vct_logit_controls_desc* d, void* stream);
+/* ---------------------------------------------------------------------------------------------
  * One stage of the greedy-decode step at SMALL batch (B <= 4): out[b, n] = epilogue(W[n, :] . prologue(...)[b, :]), a weight-
  * streaming matrix-vector kernel whose prologue builds the input vector and whose epilogue finishes the stage, so that the
  * embedding / LayerNorm / attention launches of the per-token step vanish into their consumers (csrc/vct_decode.hip):

@@ -6,7 +6,9 @@ to the token ids (vct_amd.vision.ClipVisionTower -> evaluate.v2t_frames).
 --frames: a directory of images (read with PIL in name order, converted to RGB; all of one size) or an .npy of uint8 [T, H, W, 3] RGB
 frames.  Decoding the video and choosing which frames to keep are the caller's: no decoder and no sampling policy are shipped.
 --clip-weights: a CLIP state dict in OpenAI's or transformers' key convention (ViT-B/32; --clip-prefix clip. for a CLIP4Clip
-checkpoint); no weights are shipped either.  --greedy is the default; --beam K searches K beams.  Prints `id<TAB>caption`."""
+checkpoint); no weights are shipped either.  --greedy is the default; --beam K searches K beams.  Generation controls (both
+decoders; vct_amd.decode.GenerationControls): --min-length N (no end token before N tokens), --no-repeat-ngram N (no n-gram twice),
+--repetition-penalty THETA (>= 1), --ban ID [ID ...] (token ids that are never emitted).  Prints `id<TAB>caption`."""
 import argparse
 import os
 import sys
@@ -48,10 +50,19 @@ def main():
     mode.add_argument("--beam", type=int, default=None, metavar="K")
     ap.add_argument("--max-len", type=int, default=30)
     ap.add_argument("--fp32", action="store_true", help="parity mode: fp32 GEMM operands in the tower and the model")
+    ap.add_argument("--min-length", type=int, default=0, metavar="N", help="at least N tokens before the end token")
+    ap.add_argument("--no-repeat-ngram", type=int, default=0, metavar="N", help="no n-gram of this size twice in a caption (0 = off, at most 8)")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0, metavar="THETA", help="1 = off, at most 16")
+    ap.add_argument("--ban", type=int, nargs="+", default=[], metavar="ID", help="token ids that are never emitted (at most 32)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("predict_frames.py runs on the GPU; there is none here")
     from vct_amd import checkpoint, evaluate
+    from vct_amd.decode import GenerationControls
+    try:
+        controls = GenerationControls(args.min_length, args.no_repeat_ngram, args.repetition_penalty, args.ban)
+    except ValueError as e:
+        raise SystemExit(str(e))
     from vct_amd.model import MMT4Caption
     from vct_amd.utils import Config
     from vct_amd.vision import ClipVisionTower
@@ -64,7 +75,7 @@ def main():
     checkpoint.load_weights(model, args.model)
     tower = ClipVisionTower.from_file(args.clip_weights, dev, dtype, prefix=args.clip_prefix)
     videos = [read_frames(p) for p in args.frames]
-    captions = evaluate.v2t_frames(model, tower, videos, max_len=args.max_len, beam_size=args.beam)
+    captions = evaluate.v2t_frames(model, tower, videos, max_len=args.max_len, beam_size=args.beam, controls=controls)
     for p, c in zip(args.frames, captions):
         print(f"{os.path.splitext(os.path.basename(os.path.normpath(p)))[0]}\t{c}")
 

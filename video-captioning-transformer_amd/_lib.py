@@ -216,6 +216,23 @@ class SampleSelectDesc(C.Structure):
                 ("seq_logp", vp), ("ctl", vp), ("workspace", vp), ("workspace_bytes", i64)]
 
 
+LOGIT_BANNED_MAX = 32
+
+
+class LogitCtl(C.Structure):
+    """include/vct_hip.h, vct_logit_ctl: the generation controls vct_logit_controls reads from device memory."""
+    _c_name_ = "vct_logit_ctl"
+    _fields_ = [("min_length", i32), ("ngram", i32), ("theta", f32), ("inv_theta", f32), ("n_banned", i32), ("reserved", i32 * 3),
+                ("banned", i32 * LOGIT_BANNED_MAX)]
+
+
+class LogitControlsDesc(C.Structure):
+    """include/vct_hip.h, vct_logit_controls_desc: the logit rules of one decode step, in place."""
+    _c_name_ = "vct_logit_controls_desc"
+    _fields_ = [("dtype", i32), ("rows", i32), ("V", i32), ("t", i32), ("x", vp), ("ldx", i64), ("end_id", i64), ("ids", vp),
+                ("ids_stride", i64), ("ended", vp), ("parents", vp), ("parents_stride", i64), ("K", i32), ("reserved", i32), ("ctl", vp)]
+
+
 CIDER_MAX_LEN, CIDER_MAX_ORDER = 64, 4
 
 
@@ -330,6 +347,7 @@ _SIGS = {
     "vct_beam_reorder": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, i64, vp]),
     "vct_sample_select_workspace_bytes": (i64, [C.c_int, C.c_int, C.c_int]),
     "vct_sample_select": (C.c_int, [C.POINTER(SampleSelectDesc), vp]),
+    "vct_logit_controls": (C.c_int, [C.POINTER(LogitControlsDesc), vp]),
     "vct_gather_pad_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
     "vct_adam_step": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, i64, i64, i32, vp, vp]),
     "vct_adam_step_pk": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, i64, i64, i32, vp, vp, C.c_int, i64, vp]),

@@ -11,9 +11,12 @@ class DecodeState:
     cache [B, Lmax, 3d] (packed q | k | v of every consumed token), per-layer cross-attention K/V of the memory (computed once), step temporaries
     and the hipGraphs of the per-token step (one per position; every kernel argument is baked)."""
 
-    def __init__(self, eng: "DecoderEngine", Bn: int, Te: int, Lmax: int, return_attn: bool = False):
+    def __init__(self, eng: "DecoderEngine", Bn: int, Te: int, Lmax: int, return_attn: bool = False, controls: bool = False):
         d, L, dt, dev = eng.cfg["d"], eng.cfg["layers"], eng.dt, eng.dev
         self.B, self.Te, self.Lmax = Bn, Te, Lmax
+        # controls: the 160-byte block {min_length, ngram, theta, inv_theta, n_banned, reserved[3], banned[32]} that vct_logit_controls
+        # reads on the device (the captured graphs serve every setting); None = the step issues no controls launch at all
+        self.gen_ctl = torch.zeros(40, dtype=torch.int32, device=dev) if controls else None
         # return_attn: row t-1 of layer l = the head-averaged cross-attention of the token consumed at step t (predict_video.py:63-64);
         # None = the step issues no map launch at all
         self.attn_maps = torch.zeros(Bn, L, max(Lmax - 1, 1), Te, dtype=torch.float32, device=dev) if return_attn else None
@@ -26,6 +29,13 @@ class DecodeState:
         self.b = _Buf(dev, eng.ps.ctx)
         self.graphs = {}
 
+    def set_controls(self, controls):
+        """Write the generation controls of the next run (decode.GenerationControls) into gen_ctl: one 160-byte host -> device
+        copy on the current stream, no recapture."""
+        if self.gen_ctl is None:
+            raise ValueError("this decode session was built without generation controls")
+        self.gen_ctl.copy_(torch.frombuffer(bytearray(controls.pack()), dtype=torch.int32))
+
     def slot(self, l: int, t: int) -> torch.Tensor:
         """Slot t-1 of layer l's self-attention cache, q | k | v of the token consumed at step t: a [B, 3d] view, row stride Lmax*3d."""
         return self.kv_self[l].view(self.B, self.Lmax, -1)[:, t - 1, :]
@@ -36,9 +46,21 @@ def _greedy_stage(eng, st: DecodeState, logits: torch.Tensor, t: int, end_id: in
     ops.greedy_select(logits, st.ys[:, t], end_id, st.ended, st.ended_count, st.all_ended_at, t, cols=eng.V)
 
 
+def _controls_stage(eng, st: DecodeState, logits: torch.Tensor, t: int, end_id: int):
+    """Generation controls of a session that carries them: one vct_logit_controls launch edits the step's logits in place in
+    front of the selection stage.  Beams: on the token table and parent rows as they stand before vct_beam_select of step t."""
+    if isinstance(st, BeamDecodeState):
+        ops.logit_controls(logits, st.ys, st.finished, st.gen_ctl, t, end_id, cols=eng.V, parents=st.parents, K=st.K)
+    else:
+        ops.logit_controls(logits, st.ys, st.ended, st.gen_ctl, t, end_id, cols=eng.V)
+
+
 def _finish_step(eng, st: DecodeState, logits: torch.Tensor, t: int, end_id: int, select):
-    """The end of every step variant that takes `select`: publish the step's logits, run the selection stage (None = greedy)."""
-    st.last_logits = logits          # [B, Vp] of this step (decode.teacher_forced_next_ids reads it)
+    """The end of every step variant that takes `select`: publish the step's logits, apply the session's generation controls (if
+    it carries any), run the selection stage (None = greedy)."""
+    st.last_logits = logits          # [B, Vp] of this step (decode.teacher_forced_next_ids reads it); after the controls, if any
+    if st.gen_ctl is not None:
+        _controls_stage(eng, st, logits, t, end_id)
     (select or _greedy_stage)(eng, st, logits, t, end_id)
 
 
@@ -279,8 +301,10 @@ def _decoder_decode_step_fused(eng, st: DecodeState, t: int, end_id: int, select
 
 
 def decode_step_variant(eng, st: DecodeState, select=None) -> str:
-    """The step variant of this session, 'block' | 'gemv' | 'fused' | 'generic': what _decoder_decode_step_any dispatches on."""
-    if select is None and _decoder_block_decode_ok(eng, st):
+    """The step variant of this session, 'block' | 'gemv' | 'fused' | 'generic': what _decoder_decode_step_any dispatches on.  The
+    block step fuses its own greedy selection into the generator launch: a session with another selection stage or with
+    generation controls (which run between the generator and the selection) takes the gemv / fused / generic step."""
+    if select is None and st.gen_ctl is None and _decoder_block_decode_ok(eng, st):
         return "block"
     if _decoder_small_decode_ok(eng, st):
         return "gemv"
@@ -306,8 +330,8 @@ class BeamDecodeState(DecodeState):
     the token appended at step t), per-step finished counters int32 [Lmax], all_ended_at = the first step after which every
     slot is finished."""
 
-    def __init__(self, eng: "DecoderEngine", Bv: int, K: int, Te: int, Lmax: int):
-        super().__init__(eng, Bv * K, Te, Lmax)      # (no attention maps: they would have to follow the parent back-track)
+    def __init__(self, eng: "DecoderEngine", Bv: int, K: int, Te: int, Lmax: int, controls: bool = False):
+        super().__init__(eng, Bv * K, Te, Lmax, controls=controls)      # (no attention maps: they would have to follow the parent back-track)
         d, L, dt, dev = eng.cfg["d"], eng.cfg["layers"], eng.dt, eng.dev
         M = Bv * K
         self.Bv, self.K = Bv, K
@@ -359,8 +383,8 @@ class SampleDecodeState(DecodeState):
     device (the captured graphs serve every setting), step_logp fp32 [Lmax, M] (row t: the log-probability of the token drawn
     at step t, 0 for a row that had ended), seq_logp fp32 [M] (their sum) and the selection workspace."""
 
-    def __init__(self, eng: "DecoderEngine", Bv: int, N: int, Te: int, Lmax: int):
-        super().__init__(eng, Bv * N, Te, Lmax)      # (no attention maps: return_attn is a greedy-decode feature)
+    def __init__(self, eng: "DecoderEngine", Bv: int, N: int, Te: int, Lmax: int, controls: bool = False):
+        super().__init__(eng, Bv * N, Te, Lmax, controls=controls)      # (no attention maps: return_attn is a greedy-decode feature)
         dev = eng.dev
         M = Bv * N
         self.Bv, self.N = Bv, N

@@ -29,12 +29,12 @@ def _check_sample(sample, beam_size, return_attn):
 
 
 @torch.no_grad()
-def _decode(model, feats, masks, max_len, beam_size, return_attn=False, sample=None):
+def _decode(model, feats, masks, max_len, beam_size, return_attn=False, sample=None, controls=None):
     if sample is not None:
-        return model.sample_decode(feats, masks, max_len=max_len, **sample)
+        return model.sample_decode(feats, masks, max_len=max_len, controls=controls, **sample)
     if beam_size is None:
-        return model.greedy_decode(feats, masks, max_len=max_len, return_attn=return_attn)
-    return model.beam_decode(feats, masks, beam_size=beam_size, max_len=max_len, return_attn=return_attn)
+        return model.greedy_decode(feats, masks, max_len=max_len, return_attn=return_attn, controls=controls)
+    return model.beam_decode(feats, masks, beam_size=beam_size, max_len=max_len, return_attn=return_attn, controls=controls)
 
 
 def average_attention(maps: torch.Tensor, length: Optional[int] = None) -> torch.Tensor:
@@ -49,35 +49,37 @@ def average_attention(maps: torch.Tensor, length: Optional[int] = None) -> torch
 
 @torch.no_grad()
 def v2t_batch(model, video_feats: Sequence[torch.Tensor], video_masks: Optional[Sequence[torch.Tensor]], max_len: int = 30,
-              beam_size: Optional[int] = None, return_attn: bool = False, sample: Optional[dict] = None):
+              beam_size: Optional[int] = None, return_attn: bool = False, sample: Optional[dict] = None, controls=None):
     """eval.py:126-145: video_feats = list (one per modality) of [B, T, E]; masks = list of bool [B, T] or None.
     beam_size: None = greedy (the reference's only mode), else beam search with that many beams (MMT4Caption.beam_decode).
     return_attn (greedy only): (captions, cross-attention maps fp32 [B, layers, steps, Te]) -- MMT4Caption.greedy_decode_ids.
     sample = dict(num_samples=..., temperature=..., top_k=..., top_p=..., seed=...) (any subset): sampled decoding
     (MMT4Caption.sample_decode); returns for every video the list of its num_samples captions.  Excludes beam_size and
-    return_attn (ValueError)."""
+    return_attn (ValueError).  controls: a decode.GenerationControls (minimum length, no-repeat n-gram ban, repetition penalty,
+    banned ids) for whichever decoder runs; combines with beam_size, sample and return_attn."""
     _check_sample(sample, beam_size, return_attn)
     model.eval()
     dev = model.device
     video_feats = [f.to(dev, non_blocking=True) for f in video_feats]
     video_masks = [m.to(dev, non_blocking=True) for m in video_masks] if video_masks is not None else None
     if return_attn:
-        caps, maps = _decode(model, video_feats, video_masks, max_len, beam_size, True)
+        caps, maps = _decode(model, video_feats, video_masks, max_len, beam_size, True, controls=controls)
         return [_strip_special(r) for r in caps], maps
     if sample is not None:
-        return [[_strip_special(r) for r in caps] for caps in _decode(model, video_feats, video_masks, max_len, None, sample=sample)]
-    return [_strip_special(r) for r in _decode(model, video_feats, video_masks, max_len, beam_size)]
+        return [[_strip_special(r) for r in caps]
+                for caps in _decode(model, video_feats, video_masks, max_len, None, sample=sample, controls=controls)]
+    return [_strip_special(r) for r in _decode(model, video_feats, video_masks, max_len, beam_size, controls=controls)]
 
 
 @torch.no_grad()
 def v2t_frames(model, tower, videos: Sequence[torch.Tensor], max_len: int = 30, beam_size: Optional[int] = None,
                return_attn: bool = False, sample: Optional[dict] = None, extra_feats: Optional[Sequence[torch.Tensor]] = None,
-               extra_masks: Optional[Sequence[torch.Tensor]] = None):
+               extra_masks: Optional[Sequence[torch.Tensor]] = None, controls=None):
     """predict_video.py --video, batched: videos = list of uint8 [T_i, H_i, W_i, 3] RGB frames (lengths and sizes may differ), tower =
     a vision.ClipVisionTower.  Each video is encoded on the device into its rows of ONE padded [B, max T_i, dim] matrix (padding
     rows zero, mask True there) and that goes to v2t_batch with its keywords: no feature visits the host.  A model with more than
     one feature stream takes the other streams' precomputed features as extra_feats (list of [B, T, E], in modal order behind the
-    first) with extra_masks (list of bool [B, T], or None when nothing is padded)."""
+    first) with extra_masks (list of bool [B, T], or None when nothing is padded).  controls: as v2t_batch."""
     _check_sample(sample, beam_size, return_attn)
     shapes = list(model.model_config["modal_shape"])
     if tower.dim != shapes[0]:
@@ -102,33 +104,34 @@ def v2t_frames(model, tower, videos: Sequence[torch.Tensor], max_len: int = 30, 
     if ragged or extra_masks is not None:
         others = list(extra_masks) if extra_masks is not None else [torch.zeros(f.shape[:2], dtype=torch.bool) for f in extra_feats]
         masks = [mask] + others
-    return v2t_batch(model, [feats] + extra_feats, masks, max_len=max_len, beam_size=beam_size, return_attn=return_attn, sample=sample)
+    return v2t_batch(model, [feats] + extra_feats, masks, max_len=max_len, beam_size=beam_size, return_attn=return_attn, sample=sample,
+                     controls=controls)
 
 
 @torch.no_grad()
 def v2t_single(model, video_feat: Sequence[torch.Tensor], max_len: int = 30, beam_size: Optional[int] = None,
-               return_attn: bool = False, sample: Optional[dict] = None):
+               return_attn: bool = False, sample: Optional[dict] = None, controls=None):
     """train.py:194-203: one video (list of [T, E] per modality), no mask.  return_attn: (caption, maps fp32 [layers, steps, Te]).
-    sample (see v2t_batch): the list of the video's num_samples sampled captions."""
+    sample (see v2t_batch): the list of the video's num_samples sampled captions.  controls: as v2t_batch."""
     _check_sample(sample, beam_size, return_attn)
     model.eval()
     feats = [f.unsqueeze(0).to(model.device) for f in video_feat]
     if return_attn:
-        caps, maps = _decode(model, feats, None, max_len, beam_size, True)
+        caps, maps = _decode(model, feats, None, max_len, beam_size, True, controls=controls)
         return _strip_special(caps[0]), maps[0]
     if sample is not None:
-        return [_strip_special(r) for r in _decode(model, feats, None, max_len, None, sample=sample)[0]]
-    return _strip_special(_decode(model, feats, None, max_len, beam_size)[0])
+        return [_strip_special(r) for r in _decode(model, feats, None, max_len, None, sample=sample, controls=controls)[0]]
+    return _strip_special(_decode(model, feats, None, max_len, beam_size, controls=controls)[0])
 
 
 @torch.no_grad()
-def eval_epoch(model, dataloader, max_len: int = 30, beam_size: Optional[int] = None) -> Dict[str, str]:
+def eval_epoch(model, dataloader, max_len: int = 30, beam_size: Optional[int] = None, controls=None) -> Dict[str, str]:
     """train.py:171-180 / eval.py:156-160 without the scorer: captions for every video a by_video loader yields
-    -> {vid: caption}.  Decoding is batched (the reference's eval config uses batch_size 1)."""
+    -> {vid: caption}.  Decoding is batched (the reference's eval config uses batch_size 1).  controls: as v2t_batch."""
     model.eval()
     vid2result: Dict[str, str] = {}
     for v_feats, v_masks, _caps, vids in dataloader:
-        vid2result.update(zip(vids, v2t_batch(model, v_feats, v_masks, max_len=max_len, beam_size=beam_size)))
+        vid2result.update(zip(vids, v2t_batch(model, v_feats, v_masks, max_len=max_len, beam_size=beam_size, controls=controls)))
     return vid2result
 
 
@@ -205,9 +208,9 @@ def _word_rows(scorer, captions: Sequence[str], device) -> torch.Tensor:
 
 @torch.no_grad()
 def eval_metrics(model, dataloader, max_len: int = 30, beam_size: Optional[int] = None, level: str = "token", scorer=None,
-                 return_captions: bool = False):
+                 return_captions: bool = False, controls=None):
     """train.py:171-192 / eval.py:156-168 with the scoring on the device: decodes every video a by_video loader yields (greedy, or
-    beam search with beam_size beams) and returns {Bleu_1..4, ROUGE_L, CIDEr, sum} (metrics.py), or (that, {vid: caption} exactly
+    beam search with beam_size beams; controls: a decode.GenerationControls for that decoder) and returns {Bleu_1..4, ROUGE_L, CIDEr, sum} (metrics.py), or (that, {vid: caption} exactly
     as eval_epoch returns it) with return_captions.
 
     level "token": the references are the loader's dataset.video2caption tokenised once by the model's caption preprocessor; the
@@ -242,9 +245,9 @@ def eval_metrics(model, dataloader, max_len: int = 30, beam_size: Optional[int] 
         v_feats = [f.to(dev, non_blocking=True) for f in v_feats]
         v_masks = [m.to(dev, non_blocking=True) for m in v_masks] if v_masks is not None else None
         if beam_size is None:
-            ys = model.greedy_decode_ids(v_feats, v_masks, max_len=max_len)
+            ys = model.greedy_decode_ids(v_feats, v_masks, max_len=max_len, controls=controls)
         else:
-            ys = model.beam_decode_ids(v_feats, v_masks, beam_size=beam_size, max_len=max_len)
+            ys = model.beam_decode_ids(v_feats, v_masks, beam_size=beam_size, max_len=max_len, controls=controls)
         caps = None
         if level == "word" or return_captions:
             caps = [_strip_special(c) for c in model._ids_to_captions(ys)]

@@ -552,12 +552,13 @@ class MMT4Caption(nn.Module):
 
     @torch.no_grad()
     def greedy_decode(self, video_feat: List[torch.Tensor], video_masks: Optional[List[torch.Tensor]] = None,
-                      max_len: int = 30, return_attn: bool = False):
-        """return_attn: (captions, maps fp32 [B, layers, steps, Te]) -- see greedy_decode_ids."""
+                      max_len: int = 30, return_attn: bool = False, controls=None):
+        """return_attn: (captions, maps fp32 [B, layers, steps, Te]) -- see greedy_decode_ids.  controls: a
+        decode.GenerationControls (minimum length, no-repeat n-gram ban, repetition penalty, banned ids)."""
         if return_attn:
-            ys, maps = self.greedy_decode_ids(video_feat, video_masks, max_len, return_attn=True)
+            ys, maps = self.greedy_decode_ids(video_feat, video_masks, max_len, return_attn=True, controls=controls)
             return self._ids_to_captions(ys), maps
-        return self._ids_to_captions(self.greedy_decode_ids(video_feat, video_masks, max_len))
+        return self._ids_to_captions(self.greedy_decode_ids(video_feat, video_masks, max_len, controls=controls))
 
     def _ids_to_captions(self, ys: torch.Tensor) -> List[str]:
         end_id = self.cap_preprocessor.end_id
@@ -575,12 +576,13 @@ class MMT4Caption(nn.Module):
 
     @torch.no_grad()
     def greedy_decode_ids(self, video_feat, video_masks=None, max_len: int = 30, kv_cache: bool = True,
-                          use_graphs: bool = True, return_attn: bool = False):
+                          use_graphs: bool = True, return_attn: bool = False, controls=None):
         """The id matrix ys [B, <=max_len] of MMT4Caption.greedy_decode (MMT4Caption.py:159-172).
         kv_cache=False runs the reference's O(L^2) algorithm (full decoder re-run per token).
         return_attn (KV cache only; any model, with or without caption_decoder.layer_type): (ys, maps) with maps fp32
         [B, layers, ys.shape[1] - 1, Te], row t-1 = the head-averaged cross-attention of the token consumed at step t
-        (predict_video.py --vis_attn)."""
+        (predict_video.py --vis_attn).  controls: a decode.GenerationControls; every step's arg-max is then taken from the processed
+        logits (semantics: decode.GenerationControls), on either path."""
         if return_attn and not kv_cache:
             raise ValueError("return_attn needs the KV-cached decode (kv_cache=True)")
         was_training = self.training
@@ -589,26 +591,30 @@ class MMT4Caption(nn.Module):
             from .. import decode
             feats, mask = self._video_inputs(video_feat, video_masks)
             if kv_cache:
-                return decode.greedy_decode_ids(self, feats, mask, max_len, use_graphs=use_graphs, return_attn=return_attn)
-            return decode.greedy_decode_ids_reference_algorithm(self, feats, mask, max_len)
+                return decode.greedy_decode_ids(self, feats, mask, max_len, use_graphs=use_graphs, return_attn=return_attn,
+                                                controls=controls)
+            return decode.greedy_decode_ids_reference_algorithm(self, feats, mask, max_len, controls=controls)
         finally:
             self.train(was_training)
 
     @torch.no_grad()
     def beam_decode(self, video_feat: List[torch.Tensor], video_masks: Optional[List[torch.Tensor]] = None, beam_size: int = 5,
-                    max_len: int = 30, length_penalty: float = 1.0, return_attn: bool = False) -> List[str]:
+                    max_len: int = 30, length_penalty: float = 1.0, return_attn: bool = False, controls=None) -> List[str]:
         """Beam-search captions, one string per video (the reference's beam_decode is `pass`, MMT4Caption.py:186); ids -> text
         as greedy_decode.  Semantics: decode.beam_decode_ids.  return_attn=True raises ValueError: attention maps would have to
-        follow the beams' parent back-track (greedy decoding returns them)."""
+        follow the beams' parent back-track (greedy decoding returns them).  controls: a decode.GenerationControls; the beam scores
+        are then log-probabilities under the controlled distribution."""
         from ..decode import _no_beam_attn
         _no_beam_attn(return_attn)
-        return self._ids_to_captions(self.beam_decode_ids(video_feat, video_masks, beam_size, max_len, length_penalty))
+        return self._ids_to_captions(self.beam_decode_ids(video_feat, video_masks, beam_size, max_len, length_penalty, controls=controls))
 
     @torch.no_grad()
     def beam_decode_ids(self, video_feat, video_masks=None, beam_size: int = 5, max_len: int = 30, length_penalty: float = 1.0,
-                        kv_cache: bool = True, use_graphs: bool = True, return_all: bool = False, return_attn: bool = False):
+                        kv_cache: bool = True, use_graphs: bool = True, return_all: bool = False, return_attn: bool = False,
+                        controls=None):
         """The best beam's id matrix [B, <=max_len] (return_all: (ids [B, K, L'], final scores [B, K])) of beam_decode.
-        kv_cache=False runs the reference algorithm (full decoder re-run per token, host-side selection)."""
+        kv_cache=False runs the reference algorithm (full decoder re-run per token, host-side selection).  controls: a
+        decode.GenerationControls, on either path."""
         from ..decode import _no_beam_attn
         _no_beam_attn(return_attn)
         was_training = self.training
@@ -618,19 +624,20 @@ class MMT4Caption(nn.Module):
             feats, mask = self._video_inputs(video_feat, video_masks)
             if kv_cache:
                 return decode.beam_decode_ids(self, feats, mask, beam_size, max_len, length_penalty,
-                                              use_graphs=use_graphs, return_all=return_all)
+                                              use_graphs=use_graphs, return_all=return_all, controls=controls)
             return decode.beam_decode_ids_reference_algorithm(self, feats, mask, beam_size, max_len, length_penalty,
-                                                              return_all=return_all)[0]
+                                                              return_all=return_all, controls=controls)[0]
         finally:
             self.train(was_training)
 
     @torch.no_grad()
     def sample_decode(self, video_feat: List[torch.Tensor], video_masks: Optional[List[torch.Tensor]] = None, num_samples: int = 1,
                       max_len: int = 30, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed=None,
-                      kv_cache: bool = True) -> List[List[str]]:
+                      kv_cache: bool = True, controls=None) -> List[List[str]]:
         """Sampled captions: for every video a list of num_samples strings (ids -> text as greedy_decode).  Semantics:
-        decode.sample_decode_ids."""
-        ids = self.sample_decode_ids(video_feat, video_masks, num_samples, max_len, temperature, top_k, top_p, seed, kv_cache)
+        decode.sample_decode_ids.  controls: a decode.GenerationControls; tokens are then drawn from the controlled distribution."""
+        ids = self.sample_decode_ids(video_feat, video_masks, num_samples, max_len, temperature, top_k, top_p, seed, kv_cache,
+                                     controls=controls)
         B, N = ids.shape[0], ids.shape[1]
         flat = self._ids_to_captions(ids.reshape(B * N, -1))
         return [flat[b * N:(b + 1) * N] for b in range(B)]
@@ -638,9 +645,10 @@ class MMT4Caption(nn.Module):
     @torch.no_grad()
     def sample_decode_ids(self, video_feat, video_masks=None, num_samples: int = 1, max_len: int = 30, temperature: float = 1.0,
                           top_k: int = 0, top_p: float = 1.0, seed=None, kv_cache: bool = True, use_graphs: bool = True,
-                          return_logp: bool = False):
+                          return_logp: bool = False, controls=None):
         """The id table [B, num_samples, <=max_len] of sample_decode (return_logp: (ids, seq_logp fp32 [B, num_samples])).
-        kv_cache=False runs the reference algorithm (full decoder re-run per token, host-side selection with the same draws)."""
+        kv_cache=False runs the reference algorithm (full decoder re-run per token, host-side selection with the same draws).
+        controls: a decode.GenerationControls; return_logp is then the log-probability under the controlled distribution."""
         from .. import decode
         decode._check_sample_args(num_samples, temperature, top_k, top_p)
         was_training = self.training
@@ -648,7 +656,7 @@ class MMT4Caption(nn.Module):
         try:
             feats, mask = self._video_inputs(video_feat, video_masks)
             kw = dict(max_len=max_len, num_samples=num_samples, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
-                      return_logp=return_logp)
+                      return_logp=return_logp, controls=controls)
             if kv_cache:
                 return decode.sample_decode_ids(self, feats, mask, use_graphs=use_graphs, **kw)
             return decode.sample_decode_ids_reference_algorithm(self, feats, mask, **kw)[0]

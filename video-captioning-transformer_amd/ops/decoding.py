@@ -1,5 +1,5 @@
 """Caption decoding: greedy / beam / sampled selection and the KV-cached decode-step kernels (csrc/vct_decode.hip,
-csrc/vct_decode_block.hip, csrc/vct_beam.hip, csrc/vct_sample.hip)."""
+csrc/vct_decode_block.hip, csrc/vct_beam.hip, csrc/vct_sample.hip, csrc/vct_logit_controls.hip)."""
 import torch
 
 from .. import _lib as L
@@ -54,6 +54,22 @@ def sample_select(x, out, end_id: int, pad_id: int, ended, ended_count, all_ende
     d.step_logp, d.seq_logp, d.ctl = step_logp.data_ptr(), seq_logp.data_ptr(), ctl.data_ptr()
     d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
     L.check(L.load().vct_sample_select(L.C.byref(d), L.stream_ptr()), "vct_sample_select")
+
+
+def logit_controls(x, ids, ended, ctl, t: int, end_id: int, cols=None, parents=None, K: int = 0):
+    """The generation controls of one decode step (include/vct_hip.h, vct_logit_controls): repetition penalty, banned ids,
+    minimum length and the no-repeat n-gram ban, in place on the logits x [rows, ldx] (columns < cols) of step t.  ids: the id
+    matrix [rows, Lmax] int64 -- or, with parents (int32 [Lmax, rows], K beams per video), the beams' token table, whose
+    histories follow the parent back-track.  ended: the session's ended / finished flags (bool or uint8 [rows]); ctl: the
+    160-byte device control block (decode.GenerationControls.pack)."""
+    d = L.LogitControlsDesc()
+    d.dtype, d.rows, d.V, d.t = L.dtype_code(x.dtype), x.shape[0], int(cols or x.shape[1]), int(t)
+    d.x, d.ldx, d.end_id = x.data_ptr(), _ld(x), int(end_id)
+    d.ids, d.ids_stride, d.ended, d.ctl = ids.data_ptr(), ids.stride(0), ended.data_ptr(), ctl.data_ptr()
+    if parents is not None:
+        d.parents, d.parents_stride, d.K = parents.data_ptr(), parents.stride(0), int(K)
+    L.check(L.load().vct_logit_controls(L.C.byref(d), L.stream_ptr()), "vct_logit_controls")
+    return x
 
 
 def decode_gemv(W, out, B, *, bias=None, pro="none", x_in=None, ln1=None, ln2=None, embed=None, attn=None, act=None, res=None,
