@@ -159,6 +159,53 @@ def test_tiny_fp32_beam_matches_numpy():
         _check_vs_numpy(m, p, cfg, z[f"{tag}/feats"], 3, 12)
 
 
+def test_step_tail_of_every_session_kind(monkeypatch):
+    """The tail of a decode step, per kind of session: generation controls (only where the session carries them) in front of the
+    session's own selection stage, beams alone hand their parent rows to the controls, and every beam step reorders the cache from
+    the ping-pong side it ran on into the other.  Eager decodes of three steps; only the names of the ops wrappers are looked at."""
+    from vct_amd import decode, ops
+    z, mc, V, cfg, p = _tiny()
+    m = build_model(mc, V, DEV, torch.float32, p)
+    feats = torch.from_numpy(z["b3/feats"]).to(DEV)
+    calls = []
+
+    def wrap(name):
+        real = getattr(ops, name)
+
+        def wrapped(*a, **k):
+            calls.append((name, a, k))
+            return real(*a, **k)
+        monkeypatch.setattr(ops, name, wrapped)
+    for name in ("greedy_select", "logit_controls", "beam_select", "beam_reorder", "sample_select"):
+        wrap(name)
+    ctl = decode.GenerationControls(min_length=1, no_repeat_ngram_size=2)
+    kw = dict(max_len=4, use_graphs=False)
+    decoders = {"greedy": (lambda c: decode.greedy_decode_ids(m, feats, None, controls=c, **kw), ["greedy_select"]),
+                "beam": (lambda c: decode.beam_decode_ids(m, feats, None, 2, controls=c, **kw), ["beam_select", "beam_reorder"]),
+                "sample": (lambda c: decode.sample_decode_ids(m, feats, None, num_samples=2, top_k=1, controls=c, **kw),
+                           ["sample_select"])}
+    for kind, (run, stage) in decoders.items():
+        for c in (None, ctl):
+            del calls[:]
+            m.__dict__.pop("_decode_sessions", None)          # the run's session is then the only one cached
+            run(c)
+            assert [n for n, _, _ in calls] == (([] if c is None else ["logit_controls"]) + stage) * 3, (kind, c)
+            for n, a, k in calls:
+                if n == "logit_controls":
+                    if kind == "beam":
+                        assert k["K"] == 2 and k["parents"] is not None
+                    else:
+                        assert k.get("parents") is None and not k.get("K") and len(a) == 6
+            if kind == "beam":
+                ((key, st),) = m.__dict__["_decode_sessions"].items()
+                assert key[0] == "beam" and ("ctl" in key) == (c is not None)
+                reorders = [a for n, a, _ in calls if n == "beam_reorder"]
+                for t, a in enumerate(reorders, start=1):
+                    assert a[0].data_ptr() == st.kv_layers[t % 2].data_ptr(), t
+                    assert a[1].data_ptr() == st.kv_layers[(t + 1) % 2].data_ptr(), t
+                assert st.kv_layers[0].data_ptr() != st.kv_layers[1].data_ptr()
+
+
 @pytest.mark.parametrize("K", [2, 4])
 def test_cfgA_fp32_beam_matches_numpy(K):
     z = load_golden("cfgA_decode.npz")

@@ -1,4 +1,4 @@
-"""Generation controls on the device (csrc/vct_logit_controls.hip, engine._controls_stage, decode.GenerationControls): the kernel
+"""Generation controls on the device (csrc/vct_logit_controls.hip, DecodeState.apply_controls, decode.GenerationControls): the kernel
 through ops.logit_controls bit for bit against the numpy restatement (tests/gen_controls_ref.py) over the whole logits matrix, in
 row and beam form; decoding end to end on a model whose logits are planted (ids predicted by a host simulation); and a real
 model, every step's processed logits against decode.apply_controls_host."""

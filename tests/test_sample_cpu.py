@@ -145,8 +145,8 @@ def test_refusals(cpu_model, monkeypatch):
 
     def boom(*a, **k):
         raise AssertionError("device work before the argument checks")
-    monkeypatch.setattr(decode, "_run_session", boom)
-    monkeypatch.setattr(decode, "_sample_session", boom)
+    monkeypatch.setattr(decode.cached, "_run_session", boom)
+    monkeypatch.setattr(decode.cached, "_session", boom)
     monkeypatch.setattr(ops, "sample_select", boom)
     bad = [dict(temperature=0.0), dict(temperature=-1.0), dict(temperature=float("inf")), dict(temperature=float("nan")),
            dict(top_k=-1), dict(top_k=65), dict(top_k=2.5), dict(top_p=0.0), dict(top_p=1.5), dict(top_p=-0.1, top_k=5),

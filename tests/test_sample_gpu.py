@@ -257,7 +257,7 @@ def test_reproducible_and_execution_modes_agree(cfgB):
     m = cfgB
     feats = _cfgB_feats(4)
     st = engine.SampleDecodeState(m.cap_decoder._engine(), 4, 3, 13, 30)
-    assert engine.decode_step_variant(m.cap_decoder._engine(), st, engine._sample_stage) == "fused"
+    assert engine.decode_step_variant(m.cap_decoder._engine(), st) == "fused"
     run = lambda **kw: decode.sample_decode_ids(m, feats, None, num_samples=3, temperature=1.0, top_k=20, top_p=0.95,
                                                 return_logp=True, **kw)
     ids, lp = run(seed=11)

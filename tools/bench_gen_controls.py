@@ -67,7 +67,6 @@ def run(quick: bool, out=None, shapes=SHAPES):
         sessions = m.__dict__["_decode_sessions"]
         (st_c,) = [st for k, st in sessions.items() if "ctl" in k]
         (st_p,) = [st for k, st in sessions.items() if "ctl" not in k]
-        select = {"greedy": None, "beam": engine._beam_stage, "sample": engine._sample_stage}[kind]
         us_p, us_c = [], []
         for _ in range(rounds):                                # rounds alternate between the two sessions
             us_p.append(_step_us(st_p, reps))
@@ -76,8 +75,8 @@ def run(quick: bool, out=None, shapes=SHAPES):
         line = json.dumps({"bench": "gen_controls", "dtype": "bfloat16", "decoder": kind, "videos": B, "per_video": N, "rows": B * N,
                            "min_length": 5, "no_repeat_ngram_size": 3, "repetition_penalty": 1.2, "rounds": rounds, "reps": reps,
                            "steps_captured": [len(st_p.graphs), len(st_c.graphs)],
-                           "variant_plain": engine.decode_step_variant(eng, st_p, select),
-                           "variant_controls": engine.decode_step_variant(eng, st_c, select),
+                           "variant_plain": engine.decode_step_variant(eng, st_p),
+                           "variant_controls": engine.decode_step_variant(eng, st_c),
                            "us_per_step_plain": round(mp, 1), "us_per_step_controls": round(mc, 1), "added_us": round(mc - mp, 1),
                            "plain_spread": round((max(us_p) - min(us_p)) / mp, 3),
                            "controls_spread": round((max(us_c) - min(us_c)) / mc, 3)})

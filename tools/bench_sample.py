@@ -65,7 +65,7 @@ def run(quick: bool, shapes=SHAPES, out=None, settings=SETTINGS):
         st_s = sessions[("sample", B, N, 13, MAX_LEN, dtype)]
         st_g = sessions[(B * N, 13, MAX_LEN, dtype)]
         for top_k, top_p in settings:
-            st_s.set_control(1, top_k, 1.0, top_p)
+            st_s.set_sampling(1, top_k, 1.0, top_p)
             us_s, us_g = [], []
             for _ in range(rounds):                       # rounds alternate between the two sessions
                 us_s.append(_step_us(st_s, reps))

@@ -4,7 +4,7 @@ import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import MODEL_CFG, T_FRAMES, D_IN  # noqa: E402
 from vct_amd.model import MMT4Caption  # noqa: E402
-from vct_amd import decode  # noqa: E402
+from vct_amd import decode, engine  # noqa: E402
 dev = torch.device("cuda", 0)
 torch.manual_seed(666)
 m = MMT4Caption(MODEL_CFG, device=dev, compute_dtype=torch.bfloat16); m.mode("caption"); m.eval()
@@ -19,7 +19,8 @@ for B in (1, 128):
         torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / 5
         print(f"B={B:3d} sync_every={se:3d} lookahead={la}: {dt / 29 * 1e6:6.1f} us/step (whole call {dt*1e3:.2f} ms)", flush=True)
     # the bare loop: graph replays only, host-timed and event-timed
-    st = decode._session(m, m.cap_decoder._engine(), B, T_FRAMES + 1, 30)
+    dec = m.cap_decoder._engine()
+    st = decode._session(m, "greedy", (B, T_FRAMES + 1, 30, dec.dt), lambda: engine.DecodeState(dec, B, T_FRAMES + 1, 30))
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize(); t0 = time.perf_counter(); e0.record()
     for t in range(1, 30):
@@ -32,7 +33,7 @@ for B in (1, 128):
     print(f"refresh_shadow: {(time.perf_counter() - t0) / 20 * 1e6:.1f} us host")
     # fixed part: encoder forward + decode_begin only
     enc, dec = m.video_encoder._engine(), m.cap_decoder._engine()
-    st = decode._session(m, dec, B, T_FRAMES + 1, 30)
+    st = decode._session(m, "greedy", (B, T_FRAMES + 1, 30, dec.dt), lambda: engine.DecodeState(dec, B, T_FRAMES + 1, 30))
     torch.cuda.synchronize(); t0 = time.perf_counter()
     for _ in range(20):
         mem = enc.forward(feats, None, False); dec.decode_begin(st, mem, 101, 0)
@@ -42,7 +43,7 @@ for B in (1, 128):
 for B in (128,):
     feats = torch.randn(B, T_FRAMES, D_IN, device=dev)
     enc, dec = m.video_encoder._engine(), m.cap_decoder._engine()
-    st = decode._session(m, dec, B, T_FRAMES + 1, 30)
+    st = decode._session(m, "greedy", (B, T_FRAMES + 1, 30, dec.dt), lambda: engine.DecodeState(dec, B, T_FRAMES + 1, 30))
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
     for rep in range(3):
         torch.cuda.synchronize(); h0 = time.perf_counter(); ev[0].record()

@@ -4,7 +4,7 @@ import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import MODEL_CFG, T_FRAMES, D_IN  # noqa: E402
 from vct_amd.model import MMT4Caption  # noqa: E402
-from vct_amd import decode  # noqa: E402
+from vct_amd import decode, engine  # noqa: E402
 dev = torch.device("cuda", 0)
 torch.manual_seed(666)
 m = MMT4Caption(MODEL_CFG, device=dev, compute_dtype=torch.bfloat16); m.mode("caption"); m.eval()
@@ -13,7 +13,7 @@ feats = torch.randn(B, T_FRAMES, D_IN, device=dev)
 for _ in range(2):
     decode.greedy_decode_ids(m, feats, None, 30)
 enc, dec = m.video_encoder._engine(), m.cap_decoder._engine()
-st = decode._session(m, dec, B, T_FRAMES + 1, 30)
+st = decode._session(m, "greedy", (B, T_FRAMES + 1, 30, dec.dt), lambda: engine.DecodeState(dec, B, T_FRAMES + 1, 30))
 pre = m.cap_preprocessor
 
 

@@ -18,9 +18,7 @@ from .inputs import first_input, memory_len, stage_inputs, static_inputs
 from .params import ParamSet, StepContext, _Buf
 from .stack import DEC_SITE, DMEM_SYNC, EMB_SITE, ENC_IN_SITE, ENC_SITE, SAMPLE_SITE, _CUS, _StackBase, _cu_count
 from .encoder import EncoderEngine, HMMEncoderEngine
-from .decode_step import (BeamDecodeState, DecodeState, SampleDecodeState, _beam_stage, _controls_stage, _decoder_beam_begin, _decoder_beam_step,
-                          _decoder_block_decode_ok, _decoder_decode_begin, _decoder_decode_step, _decoder_decode_step_any,
-                          _decoder_decode_step_block, _decoder_decode_step_fused, _decoder_decode_step_small,
-                          _decoder_fused_decode_ok, _decoder_sample_begin, _decoder_sample_step, _decoder_small_decode_ok, _greedy_stage,
-                          _sample_stage, decode_step_variant)
+from .decode_step import (BeamDecodeState, DecodeState, SampleDecodeState, _decoder_block_decode_ok, _decoder_decode_step,
+                          _decoder_decode_step_any, _decoder_decode_step_block, _decoder_decode_step_fused, _decoder_decode_step_small,
+                          _decoder_fused_decode_ok, _decoder_small_decode_ok, decode_step_variant)
 from .decoder import DecoderEngine

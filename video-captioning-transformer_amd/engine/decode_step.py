@@ -1,5 +1,8 @@
-"""Inference on the KV cache: the state of a greedy / beam / sampled decode session, the four variants of the per-token step with their
-eligibility tests, and the selection stages.  `eng` is the DecoderEngine whose weights and switches a function works on."""
+"""Inference on the KV cache: the state of a greedy / beam / sampled decode session -- the one place where the three differ: how a
+run starts, which cache a step works on, the selection stage and the generation controls in front of it -- and the four variants of
+the per-token step with their eligibility tests.  `eng` is the DecoderEngine whose weights and switches a function works on."""
+import struct
+
 import torch
 
 from .. import ops
@@ -11,9 +14,12 @@ class DecodeState:
     cache [B, Lmax, 3d] (packed q | k | v of every consumed token), per-layer cross-attention K/V of the memory (computed once), step temporaries
     and the hipGraphs of the per-token step (one per position; every kernel argument is baked)."""
 
-    def __init__(self, eng: "DecoderEngine", Bn: int, Te: int, Lmax: int, return_attn: bool = False, controls: bool = False):
+    fused_select = True     # the selection is greedy's, which the batch-1 block step fuses into its generator launch
+
+    def __init__(self, eng: "DecoderEngine", Bn: int, Te: int, Lmax: int, return_attn: bool = False, controls: bool = False, R: int = 1):
         d, L, dt, dev = eng.cfg["d"], eng.cfg["layers"], eng.dt, eng.dev
         self.B, self.Te, self.Lmax = Bn, Te, Lmax
+        self.Bv, self.R = Bn // R, R      # R rows per video: the beams / samples of a subclass; greedy has one
         # controls: the 160-byte block {min_length, ngram, theta, inv_theta, n_banned, reserved[3], banned[32]} that vct_logit_controls
         # reads on the device (the captured graphs serve every setting); None = the step issues no controls launch at all
         self.gen_ctl = torch.zeros(40, dtype=torch.int32, device=dev) if controls else None
@@ -26,8 +32,12 @@ class DecodeState:
         self.all_ended_at = torch.full((1,), Lmax, dtype=torch.long, device=dev)   # first t at which every row had ended
         self.kv_self = [torch.zeros(Bn * Lmax, 3 * d, dtype=dt, device=dev) for _ in range(L)]    # [q | k | v] per slot
         self.kv_cross = [torch.empty(Bn * Te, 2 * d, dtype=dt, device=dev) for _ in range(L)]
+        self.mem_rep = None     # a beam / sampled session allocates it: the memory replicated per row, [B * Te, d] (also when R = 1)
         self.b = _Buf(dev, eng.ps.ctx)
         self.graphs = {}
+        self.pad_id = self.last_logits = None     # last_logits: [B, Vp] of the last step, after the controls, if any
+        # decode's session loop fills these on the GPU: the captured prologue's record, second stream, pinned word, event per position
+        self.begin = self.poll_stream = self.poll_host = self.events = None
 
     def set_controls(self, controls):
         """Write the generation controls of the next run (decode.GenerationControls) into gen_ctl: one 160-byte host -> device
@@ -36,32 +46,45 @@ class DecodeState:
             raise ValueError("this decode session was built without generation controls")
         self.gen_ctl.copy_(torch.frombuffer(bytearray(controls.pack()), dtype=torch.int32))
 
+    def start(self, eng, mem: torch.Tensor, start_id: int, pad_id: int):
+        """Reset for a new run from this encoder memory (replicated per row first, in a session that holds a mem_rep): ids, end flags, cross-attention K/V of every layer."""
+        d = eng.cfg["d"]
+        if self.mem_rep is not None:
+            self.mem_rep.view(self.Bv, self.R, self.Te, d).copy_(mem.reshape(self.Bv, 1, self.Te, d).expand(-1, self.R, -1, -1))
+            mem = self.mem_rep
+        self.pad_id = int(pad_id)
+        self.ys.fill_(pad_id)
+        self.ys[:, 0] = start_id
+        self.ended.zero_()
+        self.ended_count.zero_()
+        self.all_ended_at.fill_(self.Lmax)
+        for l in range(eng.cfg["layers"]):
+            lp = f"decoder.layers.{l}.multihead_attn."
+            ops.gemm(mem, eng.W(lp + "in_proj_weight")[d:], self.kv_cross[l], bias=eng.F(lp + "in_proj_bias")[d:])
+
+    def cache(self, l: int, t: int) -> torch.Tensor:
+        """Layer l's self-attention cache at step t, [B * Lmax, 3d]."""
+        return self.kv_self[l]
+
     def slot(self, l: int, t: int) -> torch.Tensor:
         """Slot t-1 of layer l's self-attention cache, q | k | v of the token consumed at step t: a [B, 3d] view, row stride Lmax*3d."""
-        return self.kv_self[l].view(self.B, self.Lmax, -1)[:, t - 1, :]
+        return self.cache(l, t).view(self.B, self.Lmax, -1)[:, t - 1, :]
+
+    def apply_controls(self, eng, logits: torch.Tensor, t: int, end_id: int):
+        """Generation controls of a session that carries them: one vct_logit_controls launch edits the step's logits in place."""
+        ops.logit_controls(logits, self.ys, self.ended, self.gen_ctl, t, end_id, cols=eng.V)
+
+    def select(self, eng, logits: torch.Tensor, t: int, end_id: int):
+        """Selection stage of a greedy step: arg-max into column t + sticky end flags + the first step at which every row has ended."""
+        ops.greedy_select(logits, self.ys[:, t], end_id, self.ended, self.ended_count, self.all_ended_at, t, cols=eng.V)
 
 
-def _greedy_stage(eng, st: DecodeState, logits: torch.Tensor, t: int, end_id: int):
-    """Selection stage of a greedy step: arg-max into column t + sticky end flags + the first step at which every row has ended."""
-    ops.greedy_select(logits, st.ys[:, t], end_id, st.ended, st.ended_count, st.all_ended_at, t, cols=eng.V)
-
-
-def _controls_stage(eng, st: DecodeState, logits: torch.Tensor, t: int, end_id: int):
-    """Generation controls of a session that carries them: one vct_logit_controls launch edits the step's logits in place in
-    front of the selection stage.  Beams: on the token table and parent rows as they stand before vct_beam_select of step t."""
-    if isinstance(st, BeamDecodeState):
-        ops.logit_controls(logits, st.ys, st.finished, st.gen_ctl, t, end_id, cols=eng.V, parents=st.parents, K=st.K)
-    else:
-        ops.logit_controls(logits, st.ys, st.ended, st.gen_ctl, t, end_id, cols=eng.V)
-
-
-def _finish_step(eng, st: DecodeState, logits: torch.Tensor, t: int, end_id: int, select):
-    """The end of every step variant that takes `select`: publish the step's logits, apply the session's generation controls (if
-    it carries any), run the selection stage (None = greedy)."""
-    st.last_logits = logits          # [B, Vp] of this step (decode.teacher_forced_next_ids reads it); after the controls, if any
+def _finish_step(eng, st: DecodeState, logits: torch.Tensor, t: int, end_id: int):
+    """The end of every step variant but the block step: publish the logits, apply the session's controls (if any), select."""
+    st.last_logits = logits
     if st.gen_ctl is not None:
-        _controls_stage(eng, st, logits, t, end_id)
-    (select or _greedy_stage)(eng, st, logits, t, end_id)
+        st.apply_controls(eng, logits, t, end_id)
+    st.select(eng, logits, t, end_id)
 
 
 def _attn_map_row(eng, st: DecodeState, l: int, t: int, qc: torch.Tensor):
@@ -72,20 +95,7 @@ def _attn_map_row(eng, st: DecodeState, l: int, t: int, qc: torch.Tensor):
         ops.attn_weights(qc, st.kv_cross[l][:, :d], st.attn_maps[:, l, t - 1:t, :], st.B, eng.cfg["nhead"], 1, st.Te)
 
 
-def _decoder_decode_begin(eng, st: DecodeState, mem: torch.Tensor, start_id: int, pad_id: int):
-    """Encoder memory -> cross-attention K/V of every layer (once per decode); reset ids / cache."""
-    d = eng.cfg["d"]
-    st.ys.fill_(pad_id)
-    st.ys[:, 0] = start_id
-    st.ended.zero_()
-    st.ended_count.zero_()
-    st.all_ended_at.fill_(st.Lmax)
-    for l in range(eng.cfg["layers"]):
-        lp = f"decoder.layers.{l}.multihead_attn."
-        ops.gemm(mem, eng.W(lp + "in_proj_weight")[d:], st.kv_cross[l], bias=eng.F(lp + "in_proj_bias")[d:])
-
-
-def _decoder_decode_step(eng, st: DecodeState, t: int, end_id: int, select=None):
+def _decoder_decode_step(eng, st: DecodeState, t: int, end_id: int):
     """One greedy step with the KV cache: consumes token ys[:, t-1], writes ys[:, t].  Equivalent to
     CapDecoder.decode_word on ys[:, :t] + torch.max (CapDecoder.py:62-79, MMT4Caption.py:164-172): the
     keys/values of positions < t-1 are the cached projections of the same inputs."""
@@ -100,7 +110,7 @@ def _decoder_decode_step(eng, st: DecodeState, t: int, end_id: int, select=None)
         sa = lp + "self_attn."
         # ONE packed projection per token: q, k, v land in slot t-1 of the cache [B, Lmax, 3d] (k, v stay there for the
         # later steps; q is read once, through the same row stride)
-        cache = st.kv_self[l]
+        cache = st.cache(l, t)
         qkv_new = st.slot(l, t)
         ops.gemm(x, eng.W(sa + "in_proj_weight"), qkv_new, bias=eng.F(sa + "in_proj_bias"), workspace=ws)
         o = b.get(tag + "o", (Bn, d), eng.dt)
@@ -126,7 +136,7 @@ def _decoder_decode_step(eng, st: DecodeState, t: int, end_id: int, select=None)
     logits = b.get("logits", (Bn, eng.Vp), eng.dt)
     ops.gemm(y, eng.W("generator.weight"), logits, bias=eng.F("generator.bias"), n_valid=eng.V, workspace=ws)
     # selection (greedy: arg-max into column t + sticky end flags + the first step at which every row has ended: one launch), no host sync
-    _finish_step(eng, st, logits, t, end_id, select)
+    _finish_step(eng, st, logits, t, end_id)
 
 
 def _decoder_small_decode_ok(eng, st: DecodeState) -> bool:
@@ -147,7 +157,7 @@ def _decoder_small_decode_ok(eng, st: DecodeState) -> bool:
             and st.Lmax <= 64 and st.Te <= 64 and eng.dev.type == "cuda")
 
 
-def _decoder_decode_step_small(eng, st: DecodeState, t: int, end_id: int, select=None):
+def _decoder_decode_step_small(eng, st: DecodeState, t: int, end_id: int):
     """The same step as _decoder_decode_step in 6 launches per layer + 2: embedding, LayerNorms and both attention cores run in the
     prologues of the matrix-vector kernels that consume them, residual adds in the epilogues of the producers; activations
     between stages are fp32 vectors (pre-norm sums s, normalised x kept for the next residual)."""
@@ -162,7 +172,7 @@ def _decoder_decode_step_small(eng, st: DecodeState, t: int, end_id: int, select
     for l in range(L):
         lp = f"decoder.layers.{l}."
         sa, ca = lp + "self_attn.", lp + "multihead_attn."
-        cache = st.kv_self[l]                                              # [B * Lmax, 3d]: q | k | v of every consumed token
+        cache = st.cache(l, t)                                           # [B * Lmax, 3d]: q | k | v of every consumed token
         slot = st.slot(l, t)
         if l == 0:      # x = Emb[ys[:, t-1]] + pos[t-1]  ->  q | k | v into slot t-1
             ops.decode_gemv(eng.W(sa + "in_proj_weight"), slot, B, bias=eng.F(sa + "in_proj_bias"), pro="embed",
@@ -188,7 +198,7 @@ def _decoder_decode_step_small(eng, st: DecodeState, t: int, end_id: int, select
     logits = b.get("slogits", (B, eng.Vp), f32)
     ops.decode_gemv(eng.W("generator.weight"), logits, B, bias=eng.F("generator.bias"), pro="ln_ln", x_in=s3, ln1=prev_norm,
                     ln2=(eng.F("decoder.norm.weight"), eng.F("decoder.norm.bias")), n_valid=eng.V)
-    _finish_step(eng, st, logits, t, end_id, select)
+    _finish_step(eng, st, logits, t, end_id)
 
 
 def _decoder_block_decode_ok(eng, st: DecodeState) -> bool:
@@ -215,7 +225,7 @@ def _decoder_decode_step_block(eng, st: DecodeState, t: int, end_id: int):
     for l in range(L):
         lp = f"decoder.layers.{l}."
         sa, ca = lp + "self_attn.", lp + "multihead_attn."
-        cache = st.kv_self[l]                                              # [Lmax, 3d]: q | k | v of every consumed token
+        cache = st.cache(l, t)                                           # [Lmax, 3d]: q | k | v of every consumed token
         slot = cache[t - 1]
         src = (dict(embed=(st.ys[0, t - 1:t], eng.F("tgt_to_emb.weight"), eng.pos[t - 1])) if prev is None else
                dict(res=x2, res_bias=prev[0], part=f_part, ln1=prev[1]))
@@ -252,7 +262,7 @@ def _decoder_fused_decode_ok(eng, st: DecodeState) -> bool:
             and eng.dev.type == "cuda")
 
 
-def _decoder_decode_step_fused(eng, st: DecodeState, t: int, end_id: int, select=None):
+def _decoder_decode_step_fused(eng, st: DecodeState, t: int, end_id: int):
     """The same step as _decoder_decode_step in 8 launches per layer + 3 instead of 11 + 4: every projection is one skinny MFMA
     kernel (M = batch rows, K split over the waves); norm1 / norm2 / norm3 run as the prologue of the projection that consumes
     them (which also stores the normalised rows once, for the residual two launches later), the residual adds in the epilogues;
@@ -265,7 +275,7 @@ def _decoder_decode_step_fused(eng, st: DecodeState, t: int, end_id: int, select
     for l in range(L):
         lp, tag = f"decoder.layers.{l}.", f"F{l}."
         sa, ca = lp + "self_attn.", lp + "multihead_attn."
-        cache = st.kv_self[l]
+        cache = st.cache(l, t)
         slot = st.slot(l, t)                                                # q | k | v of the consumed token
         xres = b.get(tag + "xn", (Bn, d), f32)
         if prev_norm is None:                    # x = Emb[ys[:, t-1]] + pos[t-1], built in the projection's prologue
@@ -297,28 +307,25 @@ def _decoder_decode_step_fused(eng, st: DecodeState, t: int, end_id: int, select
     ops.decode_ln2(xin, prev_norm, (eng.F("decoder.norm.weight"), eng.F("decoder.norm.bias")), y)
     logits = b.get("logits", (Bn, eng.Vp), eng.dt)
     ops.gemm(y, eng.W("generator.weight"), logits, bias=eng.F("generator.bias"), n_valid=eng.V, workspace=eng.gemm_ws())
-    _finish_step(eng, st, logits, t, end_id, select)
+    _finish_step(eng, st, logits, t, end_id)
 
 
-def decode_step_variant(eng, st: DecodeState, select=None) -> str:
+def decode_step_variant(eng, st: DecodeState) -> str:
     """The step variant of this session, 'block' | 'gemv' | 'fused' | 'generic': what _decoder_decode_step_any dispatches on.  The
     block step fuses its own greedy selection into the generator launch: a session with another selection stage or with
     generation controls (which run between the generator and the selection) takes the gemv / fused / generic step."""
-    if select is None and st.gen_ctl is None and _decoder_block_decode_ok(eng, st):
+    if st.fused_select and st.gen_ctl is None and _decoder_block_decode_ok(eng, st):
         return "block"
     if _decoder_small_decode_ok(eng, st):
         return "gemv"
     return "fused" if _decoder_fused_decode_ok(eng, st) else "generic"
 
 
-def _decoder_decode_step_any(eng, st: DecodeState, t: int, end_id: int, select=None):
-    """select: the selection stage at the end of the step, (engine, state, logits, t, end_id) -> None; None = greedy.  The batch-1
-    block step fuses greedy selection into its generator launch: any other stage takes the gemv / fused / generic step."""
-    variant = decode_step_variant(eng, st, select)
-    if variant == "block":
-        return _decoder_decode_step_block(eng, st, t, end_id)
-    step = {"gemv": _decoder_decode_step_small, "fused": _decoder_decode_step_fused, "generic": _decoder_decode_step}[variant]
-    return step(eng, st, t, end_id, select)
+def _decoder_decode_step_any(eng, st: DecodeState, t: int, end_id: int):
+    """One step of any session (greedy, beam, sampled) on the variant its shape and selection stage allow."""
+    step = {"block": _decoder_decode_step_block, "gemv": _decoder_decode_step_small, "fused": _decoder_decode_step_fused,
+            "generic": _decoder_decode_step}[decode_step_variant(eng, st)]
+    return step(eng, st, t, end_id)
 
 
 class BeamDecodeState(DecodeState):
@@ -330,11 +337,12 @@ class BeamDecodeState(DecodeState):
     the token appended at step t), per-step finished counters int32 [Lmax], all_ended_at = the first step after which every
     slot is finished."""
 
+    fused_select = False
+
     def __init__(self, eng: "DecoderEngine", Bv: int, K: int, Te: int, Lmax: int, controls: bool = False):
-        super().__init__(eng, Bv * K, Te, Lmax, controls=controls)      # (no attention maps: they would have to follow the parent back-track)
+        super().__init__(eng, Bv * K, Te, Lmax, controls=controls, R=K)      # (no attention maps: they would have to follow the parent back-track)
         d, L, dt, dev = eng.cfg["d"], eng.cfg["layers"], eng.dt, eng.dev
-        M = Bv * K
-        self.Bv, self.K = Bv, K
+        M, self.K = Bv * K, K
         self.kv_self = None
         self.kv_layers = [torch.zeros(L, M * Lmax, 3 * d, dtype=dt, device=dev) for _ in range(2)]
         self.mem_rep = torch.empty(M * Te, d, dtype=dt, device=dev)
@@ -344,35 +352,29 @@ class BeamDecodeState(DecodeState):
         self.fin_count = torch.zeros(Lmax, dtype=torch.int32, device=dev)
         nws = ops.beam_select_workspace_bytes(torch.float32, Bv, K, eng.V) // 4     # fp32 logits (the gemv step's) need the most
         self.sel_ws = torch.empty(max(nws, 1), dtype=torch.float32, device=dev)
-        self.pad_id = None
 
+    def start(self, eng, mem: torch.Tensor, start_id: int, pad_id: int):
+        """+ the beam state of step 0: slot 0 of every video scores 0, the others -inf (step 1 expands slot 0 only), nothing finished."""
+        super().start(eng, mem, start_id, pad_id)
+        self.scores.fill_(float("-inf"))
+        self.scores.view(self.Bv, self.K)[:, 0] = 0.0
+        self.finished.zero_()
+        self.fin_count.zero_()
 
-def _decoder_beam_begin(eng, st: BeamDecodeState, mem: torch.Tensor, start_id: int, pad_id: int):
-    """_decoder_decode_begin on the memory replicated to every beam's row + the beam state of step 0: slot 0 of every video
-    scores 0, the others -inf (so step 1 expands slot 0 only), nothing finished."""
-    d, Te = eng.cfg["d"], st.Te
-    st.mem_rep.view(st.Bv, st.K, Te, d).copy_(mem.reshape(st.Bv, 1, Te, d).expand(-1, st.K, -1, -1))
-    _decoder_decode_begin(eng, st, st.mem_rep, start_id, pad_id)
-    st.pad_id = int(pad_id)
-    st.scores.fill_(float("-inf"))
-    st.scores.view(st.Bv, st.K)[:, 0] = 0.0
-    st.finished.zero_()
-    st.fin_count.zero_()
+    def cache(self, l: int, t: int) -> torch.Tensor:
+        """Step t runs on side t % 2 of the ping-pong pair."""
+        return self.kv_layers[t % 2][l]
 
+    def apply_controls(self, eng, logits: torch.Tensor, t: int, end_id: int):
+        """On the token table and parent rows as they stand before vct_beam_select of step t."""
+        ops.logit_controls(logits, self.ys, self.finished, self.gen_ctl, t, end_id, cols=eng.V, parents=self.parents, K=self.K)
 
-def _beam_stage(eng, st: BeamDecodeState, logits: torch.Tensor, t: int, end_id: int):
-    """Selection stage of a beam step: top K per video (vct_beam_select), then the cache slots < t follow their parents into the
-    other side of the ping-pong pair (vct_beam_reorder)."""
-    ops.beam_select(logits, st.Bv, st.K, st.scores, st.finished, st.parents[t], st.ys[:, t], end_id, st.pad_id,
-                    st.fin_count[t:t + 1], st.all_ended_at, t, st.sel_ws, cols=eng.V)
-    ops.beam_reorder(st.kv_layers[t % 2], st.kv_layers[(t + 1) % 2], st.parents[t], st.B, st.Lmax, eng.cfg["d"], t)
-
-
-def _decoder_beam_step(eng, st: BeamDecodeState, t: int, end_id: int):
-    """One beam step: the decode step of M = B*K rows on cache side t % 2, with the beam selection stage."""
-    st.kv_self = list(st.kv_layers[t % 2].unbind(0))
-    return _decoder_decode_step_any(eng, st, t, end_id, select=_beam_stage)
-
+    def select(self, eng, logits: torch.Tensor, t: int, end_id: int):
+        """Selection stage of a beam step: top K per video (vct_beam_select), then the cache slots < t follow their parents into
+        the other side of the ping-pong pair (vct_beam_reorder)."""
+        ops.beam_select(logits, self.Bv, self.K, self.scores, self.finished, self.parents[t], self.ys[:, t], end_id, self.pad_id,
+                        self.fin_count[t:t + 1], self.all_ended_at, t, self.sel_ws, cols=eng.V)
+        ops.beam_reorder(self.kv_layers[t % 2], self.kv_layers[(t + 1) % 2], self.parents[t], self.B, self.Lmax, eng.cfg["d"], t)
 
 
 class SampleDecodeState(DecodeState):
@@ -383,44 +385,32 @@ class SampleDecodeState(DecodeState):
     device (the captured graphs serve every setting), step_logp fp32 [Lmax, M] (row t: the log-probability of the token drawn
     at step t, 0 for a row that had ended), seq_logp fp32 [M] (their sum) and the selection workspace."""
 
+    fused_select = False
+
     def __init__(self, eng: "DecoderEngine", Bv: int, N: int, Te: int, Lmax: int, controls: bool = False):
-        super().__init__(eng, Bv * N, Te, Lmax, controls=controls)      # (no attention maps: return_attn is a greedy-decode feature)
+        super().__init__(eng, Bv * N, Te, Lmax, controls=controls, R=N)      # (no attention maps: return_attn is a greedy-decode feature)
         dev = eng.dev
-        M = Bv * N
-        self.Bv, self.N = Bv, N
+        M, self.N = Bv * N, N
         self.mem_rep = torch.empty(M * Te, eng.cfg["d"], dtype=eng.dt, device=dev)
         self.ctl = torch.zeros(4, dtype=torch.int32, device=dev)
         self.step_logp = torch.zeros(Lmax, M, dtype=torch.float32, device=dev)
         self.seq_logp = torch.zeros(M, dtype=torch.float32, device=dev)
         nws = ops.sample_select_workspace_bytes(torch.float32, M, eng.V) // 4     # fp32 logits (the gemv step's) need the most
         self.sel_ws = torch.empty(max(nws, 4), dtype=torch.float32, device=dev)
-        self.pad_id = None
 
-    def set_control(self, seed: int, top_k: int, temperature: float, top_p: float):
-        """Write the settings of the next run into ctl (one 16-byte host -> device copy on the current stream)."""
-        import struct
+    def set_sampling(self, seed: int, top_k: int, temperature: float, top_p: float):
+        """Write the sampling settings of the next run into ctl (one 16-byte host -> device copy on the current stream)."""
         raw = struct.pack("<Iiff", int(seed) & 0xFFFFFFFF, int(top_k), 1.0 / float(temperature), float(top_p))
         self.ctl.copy_(torch.frombuffer(bytearray(raw), dtype=torch.int32))
 
+    def start(self, eng, mem: torch.Tensor, start_id: int, pad_id: int):
+        """+ the log-probabilities (ctl is the caller's: it is written before the replays, not by the captured begin graph)."""
+        super().start(eng, mem, start_id, pad_id)
+        self.step_logp.zero_()
+        self.seq_logp.zero_()
 
-def _decoder_sample_begin(eng, st: SampleDecodeState, mem: torch.Tensor, start_id: int, pad_id: int):
-    """_decoder_decode_begin on the memory replicated to every sample's row + the sampling state of step 0 (ctl is the
-    caller's: it is written before the replays, not by the captured begin graph)."""
-    d, Te = eng.cfg["d"], st.Te
-    st.mem_rep.view(st.Bv, st.N, Te, d).copy_(mem.reshape(st.Bv, 1, Te, d).expand(-1, st.N, -1, -1))
-    _decoder_decode_begin(eng, st, st.mem_rep, start_id, pad_id)
-    st.pad_id = int(pad_id)
-    st.step_logp.zero_()
-    st.seq_logp.zero_()
-
-
-def _sample_stage(eng, st: SampleDecodeState, logits: torch.Tensor, t: int, end_id: int):
-    """Selection stage of a sampled step: one draw per row (vct_sample_select) into column t, its log-probability into row t
-    of step_logp and onto seq_logp, greedy's end bookkeeping."""
-    ops.sample_select(logits, st.ys[:, t], end_id, st.pad_id, st.ended, st.ended_count, st.all_ended_at, t, st.step_logp[t],
-                      st.seq_logp, st.ctl, st.sel_ws, cols=eng.V)
-
-
-def _decoder_sample_step(eng, st: SampleDecodeState, t: int, end_id: int):
-    """One sampled step: the decode step of M = B*N rows with the sampling selection stage (never the batch-1 block step)."""
-    return _decoder_decode_step_any(eng, st, t, end_id, select=_sample_stage)
+    def select(self, eng, logits: torch.Tensor, t: int, end_id: int):
+        """Selection stage of a sampled step: one draw per row (vct_sample_select) into column t, its log-probability into row t
+        of step_logp and onto seq_logp, greedy's end bookkeeping."""
+        ops.sample_select(logits, self.ys[:, t], end_id, self.pad_id, self.ended, self.ended_count, self.all_ended_at, t,
+                          self.step_logp[t], self.seq_logp, self.ctl, self.sel_ws, cols=eng.V)

@@ -189,13 +189,9 @@ class DecoderEngine(_StackBase):
         ops.gemm(last, self.W("generator.weight"), logits, bias=self.F("generator.bias"), n_valid=self.V)
         return logits[:, :self.V]
 
-    # ---- inference on the KV cache: the session state and the step variants are in decode_step.py ------------------------
-    def decode_begin(self, st, mem, start_id, pad_id): return _ds._decoder_decode_begin(self, st, mem, start_id, pad_id)
-    def decode_step(self, st, t, end_id, select=None): return _ds._decoder_decode_step_any(self, st, t, end_id, select)
-    def beam_begin(self, st, mem, start_id, pad_id): return _ds._decoder_beam_begin(self, st, mem, start_id, pad_id)
-    def beam_step(self, st, t, end_id): return _ds._decoder_beam_step(self, st, t, end_id)
-    def sample_begin(self, st, mem, start_id, pad_id): return _ds._decoder_sample_begin(self, st, mem, start_id, pad_id)
-    def sample_step(self, st, t, end_id): return _ds._decoder_sample_step(self, st, t, end_id)
+    # ---- inference on the KV cache, for every kind of session: the state and the step variants are in decode_step.py ----
+    def decode_begin(self, st, mem, start_id, pad_id): return st.start(self, mem, start_id, pad_id)
+    def decode_step(self, st, t, end_id): return _ds._decoder_decode_step_any(self, st, t, end_id)
 
     def backward(self, bucket_ready=None, on_dmem_ready=None, join: bool = True) -> torch.Tensor:
         """d(loss) = 1.  Returns d(memory) [B*Te, d].  bucket_ready(kind, layer) is called when a gradient bucket
