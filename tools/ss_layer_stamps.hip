@@ -51,12 +51,13 @@ static void run(int cross, int B, int L, int Lm, float p_drop) {
   printf("== %s layer  B %d L %d Lm %d p_drop %.1f: %.1f us per launch (events)\n", cross ? "decoder" : "encoder", B, L, Lm, p_drop, ms * 1e3 / R);
   int prev = 0;
   const char* names[64] = {0};
-  names[1] = "load x/mem + barrier"; names[2] = "qkv gemm x3 + epi + res loads"; names[3] = "barrier"; names[4] = "copy qkv"; names[5] = "self attention";
-  names[6] = "barrier"; names[7] = "copy o"; names[8] = "out_proj gemm"; names[9] = "LN1 epilogue"; names[10] = "barrier + copy a, x1";
-  names[11] = "cross q gemm + epi"; names[12] = "cross kv gemm x2 + epi"; names[13] = "barrier + copy q, kv"; names[14] = "cross attention";
-  names[15] = "barrier + copy o2"; names[16] = "cross out_proj gemm"; names[17] = "LN2 epilogue"; names[18] = "barrier + copy a2, x2";
-  for (int j = 0; j < 4; j++) { names[20 + 4 * j] = "  lin1 gemm"; names[21 + 4 * j] = "  ffn epilogue + barriers"; names[22 + 4 * j] = "  copy hpre, h"; names[23 + 4 * j] = "  lin2 gemm"; }
-  names[40] = "final LN epilogue(s)"; names[41] = "barrier + copies";
+  // the saved-tensor copies ride inside the K loop of the product that follows them (panel_to_global_slice): no phase of their own
+  names[1] = "load x/mem + barrier"; names[2] = "qkv gemm x3 + epi + res loads"; names[3] = "barrier"; names[5] = "self attention";
+  names[6] = "barrier"; names[8] = "out_proj gemm (+ copy qkv, o)"; names[9] = "LN1 epilogue"; names[10] = "barrier";
+  names[11] = "cross q gemm + epi (+ copy a, x1)"; names[12] = "cross kv gemm x2 + epi"; names[13] = "barrier"; names[14] = "cross attention";
+  names[15] = "barrier"; names[16] = "cross out_proj gemm (+ copy q, kv, o2)"; names[17] = "LN2 epilogue"; names[18] = "barrier";
+  for (int j = 0; j < 4; j++) { names[20 + 4 * j] = j ? "  lin1 gemm" : "  lin1 gemm (+ copy a2, x2 / a, x1)"; names[21 + 4 * j] = "  ffn epilogue"; names[22 + 4 * j] = "  barrier"; names[23 + 4 * j] = "  lin2 gemm (+ copy h)"; }
+  names[40] = "final LN epilogue(s)"; names[41] = "barrier + copies (f, y, y2)";
   double total = 0;
   for (int i = 1; i < 64; i++) {
     if (!names[i]) continue;

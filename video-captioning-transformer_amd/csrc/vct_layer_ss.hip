@@ -28,6 +28,19 @@
 // stores in the epilogue.  Everything the unfused backward kernels read (qkv, o, a, LayerNorm statistics, pre-activation, dropped
 // activation, ...) is first completed in an LDS panel and then copied to HBM with 16-byte row-contiguous stores by all 512 threads;
 // the dropout counter streams are those of the unfused kernels, so the unfused backward runs unchanged behind this forward.
+//
+// Nothing later in the forward waits for those copies, so they have no phase of their own: a copy is cut into its 512-vector iterations
+// and these are issued between the K steps of the NEXT K = 512 product (panel_to_global_slice as the callback of wave_gemm8_cb), beside
+// that product's weight stream.  The carrier of each copy, and why its slot is not written before the barrier behind the carrier:
+//     q | k | v (R1A..R1C), o (R0)         out_proj        LN1 writes a -> R1A behind its first barrier (AP_LATE), x1 -> R1B behind both
+//     a (R1A), x1 (R1B)                    cross q block   (encoder layer: linear1(0)); the next writers are the cross attention (o2 -> R1A,
+//                                                          behind a barrier) and the chunk loop
+//     cross q (R1C), k | v (R0), o2 (R1A)  cross out_proj  LN2 writes a2 -> R1C behind its first barrier (AP_LATE), x2 -> R0 behind both
+//     a2 (R1C), x2 (R0)                    linear1(0)      chunk 0's activation goes to R1B; R1C is chunk 1's, behind the first chunk barrier
+//     h chunk j (R1B / R0 | R1C)           linear2 slice j the buffer is rewritten by chunk j + 2, two barriers later
+//     y (R0) of a layer that has a successor in the launch: that layer's first q | k | v block (x is read-only up to the attention)
+// f (R1A) and the final norm's output (R1C) are overwritten by the next q | k | v block's epilogue with no barrier in between, and the
+// last layer of a launch has no product behind it: those copies stay synchronous.  (tests/test_layer_ss_overlap_gpu.py)
 #include "vct_layer_ss_core.h"
 
 namespace vct {
@@ -172,6 +185,8 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
     const __attribute__((address_space(4))) SsLayerW& w = kp->lw[l];     // fields are fetched (scalar loads) where they are used
     auto nrm = [](const __attribute__((address_space(4))) SsNorm& n) { return SsNorm{n.g, n.b, n.y, n.mean, n.rstd}; };
     const bool fin = p.last && l == p.nl - 1;
+    // iterations of a deferred copy (panel_to_global_slice): a [MT*16][512] panel, the q | k | v panel, the 16-row k | v panel of the memory
+    constexpr int IT1 = ss_copy_its(MT * 16, SS_D), IT3 = ss_copy_its(MT * 16, 3 * SS_D), ITKV = ss_copy_its(16, 2 * SS_D);
     // the layer's linear1 bias -> LDS (the x panel of layers l > 0 is already in R0: the previous layer's output)
     for (int v = tid; v < (p.ff >> 2); v += SS_NT) reinterpret_cast<float4*>(b1s)[v] = reinterpret_cast<const float4*>(w.b1)[v];
     SS_STAMP(0);
@@ -184,7 +199,14 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
     for (int nb = 0; nb < 3; nb++) {                       // q | k | v = x W_in^T + b_in  -> panel [32][1544] in R1A..R1C
       load_bias4(bv, w.b_qkv, nb * 512 + wave * SS_CPW, lg);
       acc_zero<MT>(acc);
-      wave_gemm<MT>(acc, R0 + aoff, SS_PSTR, 0, 8, ws, b0, b1);
+      if (nb == 0 && l > 0) {                              // carries the previous layer's y (= this x, R0: read-only until the attention)
+        bf16_t* const gy = kp->lw[l - 1].n3.y;
+        wave_gemm8_cb<MT>(acc, R0 + aoff, SS_PSTR, ws, b0, b1, [&](auto K) {
+          panel_to_global_slice<SS_D, decltype(K)::value, 0, IT1, IT1>(R0, SS_PSTR, L, gy, SS_D, grow0, 0, tid);
+        });
+      } else {
+        wave_gemm<MT>(acc, R0 + aoff, SS_PSTR, 0, 8, ws, b0, b1);
+      }
       epi_store<MT>(acc, bv, R1A, SS_QSTR, nb * 512 + wave * SS_CPW, li, lg);
     }
     // residual rows of the out_proj epilogue: out of the x panel, which is about to become the attention output panel
@@ -196,8 +218,6 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
     SS_STAMP(2);
     ss_barrier();
     SS_STAMP(3);
-    panel_to_global<3 * SS_D>(R1A, SS_QSTR, L, w.qkv, 3 * SS_D, grow0, 0, tid);
-    SS_STAMP(4);
     {
       const Dropout dr = make_dropout(p.seed, w.site_sa, p.p_drop);
       ss_attn_wave(R1A + hd0, SS_QSTR, R1A + SS_D + hd0, R1A + 2 * SS_D + hd0, SS_QSTR, L, L, p.causal, padmask, dr,
@@ -206,28 +226,36 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
     SS_STAMP(5);
     ss_barrier();
     SS_STAMP(6);
-    panel_to_global<SS_D>(R0, SS_PSTR, L, w.o, SS_D, grow0, 0, tid);
-    SS_STAMP(7);
-    {                                                      // a = o W_o^T + b_o;  x1 = LN1(x + drop(a))
+    {                                                      // a = o W_o^T + b_o;  x1 = LN1(x + drop(a)); carries the copies of q | k | v and o
       load_bias4(bv, w.b_o, wave * SS_CPW, lg);
       acc_zero<MT>(acc);
-      wave_gemm<MT>(acc, R0 + aoff, SS_PSTR, 0, 8, ws, b0, b1);
+      bf16_t* const gqkv = w.qkv; bf16_t* const go = w.o;
+      wave_gemm8_cb<MT>(acc, R0 + aoff, SS_PSTR, ws, b0, b1, [&](auto K) {
+        constexpr int k = decltype(K)::value;
+        panel_to_global_slice<3 * SS_D, k, 0, IT3, IT3 + IT1>(R1A, SS_QSTR, L, gqkv, 3 * SS_D, grow0, 0, tid);
+        panel_to_global_slice<SS_D, k, IT3, IT1, IT3 + IT1>(R0, SS_PSTR, L, go, SS_D, grow0, 0, tid);
+      });
       SS_STAMP(8);
       const Dropout dr = make_dropout(p.seed, w.site_n1, p.p_drop);
-      epi_ln<MT>(acc, bv, res, nrm(w.n1), nullptr, dr, grow0, L, R1A, R1B, nullptr, red, wave, li, lg);
+      // AP = R1A is still q of the copy other waves carry: its stores wait for the epilogue's first barrier (AP_LATE)
+      epi_ln<MT, true>(acc, bv, res, nrm(w.n1), SsNorm{}, false, dr, grow0, L, R1A, R1B, nullptr, red, wave, li, lg);
       SS_STAMP(9);
     }
     ss_barrier();
-    panel_to_global<SS_D>(R1A, SS_PSTR, L, w.a, SS_D, grow0, 0, tid);
-    panel_to_global<SS_D>(R1B, SS_PSTR, L, w.n1.y, SS_D, grow0, 0, tid);
     SS_STAMP(10);
+    // a (R1A) and x1 (R1B) ride under the next product: the cross q block, or linear1(0) of an encoder layer
+    auto copy_a_x1 = [&, ga = w.a, gx1 = w.n1.y](auto K) {
+      constexpr int k = decltype(K)::value;
+      panel_to_global_slice<SS_D, k, 0, IT1, 2 * IT1>(R1A, SS_PSTR, L, ga, SS_D, grow0, 0, tid);
+      panel_to_global_slice<SS_D, k, IT1, IT1, 2 * IT1>(R1B, SS_PSTR, L, gx1, SS_D, grow0, 0, tid);
+    };
 
     if constexpr (CROSS) {
       // ---- cross-attention block -----------------------------------------------------------------------------------------------------
       const int Lm = p.Lm;
       load_bias4(bv, w.b_cq, wave * SS_CPW, lg);               // q = x1 W_q^T + b_q -> R1C
       acc_zero<MT>(acc);
-      wave_gemm<MT>(acc, R1B + aoff, SS_PSTR, 0, 8, ws, b0, b1);
+      wave_gemm8_cb<MT>(acc, R1B + aoff, SS_PSTR, ws, b0, b1, copy_a_x1);
       epi_store<MT>(acc, bv, R1C, SS_PSTR, wave * SS_CPW, li, lg);
       SS_STAMP(11);
       for (int nb = 0; nb < 2; nb++) {                     // k | v = mem W_kv^T + b_kv -> panel [16][1032] in R0
@@ -239,8 +267,6 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
       }
       SS_STAMP(12);
       ss_barrier();
-      panel_to_global<SS_D>(R1C, SS_PSTR, L, w.cq, SS_D, grow0, 0, tid);
-      panel_to_global<2 * SS_D>(R0, SS_KVSTR, Lm, w.ckv, 2 * SS_D, (long)b * Lm, 0, tid);
       SS_STAMP(13);
       {
         const Dropout dr = make_dropout(p.seed, w.site_ca, p.p_drop);
@@ -250,7 +276,6 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
       }
       SS_STAMP(14);
       ss_barrier();
-      panel_to_global<SS_D>(R1A, SS_PSTR, L, w.co, SS_D, grow0, 0, tid);
       SS_STAMP(15);
       {                                                    // a2 = o2 W_o^T + b_o;  x2 = LN2(x1 + drop(a2)); residual x1 still in R1B
 #pragma unroll
@@ -259,15 +284,20 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
           for (int t = 0; t < SS_TPW; t++) res[m][t] = *reinterpret_cast<const BV4*>(R1B + (m * 16 + li) * SS_PSTR + ecol + t * 16);
         load_bias4(bv, w.b_co, wave * SS_CPW, lg);
         acc_zero<MT>(acc);
-        wave_gemm<MT>(acc, R1A + aoff, SS_PSTR, 0, 8, ws, b0, b1);
+        bf16_t* const gcq = w.cq; bf16_t* const gckv = w.ckv; bf16_t* const gco = w.co;
+        wave_gemm8_cb<MT>(acc, R1A + aoff, SS_PSTR, ws, b0, b1, [&](auto K) {     // carries the copies of the cross q, k | v and o
+          constexpr int k = decltype(K)::value, tot = 2 * IT1 + ITKV;
+          panel_to_global_slice<SS_D, k, 0, IT1, tot>(R1C, SS_PSTR, L, gcq, SS_D, grow0, 0, tid);
+          panel_to_global_slice<2 * SS_D, k, IT1, ITKV, tot>(R0, SS_KVSTR, Lm, gckv, 2 * SS_D, (long)b * Lm, 0, tid);
+          panel_to_global_slice<SS_D, k, IT1 + ITKV, IT1, tot>(R1A, SS_PSTR, L, gco, SS_D, grow0, 0, tid);
+        });
         SS_STAMP(16);
         const Dropout dr = make_dropout(p.seed, w.site_n2, p.p_drop);
-        epi_ln<MT>(acc, bv, res, nrm(w.n2), nullptr, dr, grow0, L, R1C, R0, nullptr, red, wave, li, lg);
+        // AP = R1C is still the q of that copy: AP_LATE (YP = R0, the k | v panel, is written behind both barriers anyway)
+        epi_ln<MT, true>(acc, bv, res, nrm(w.n2), SsNorm{}, false, dr, grow0, L, R1C, R0, nullptr, red, wave, li, lg);
         SS_STAMP(17);
       }
       ss_barrier();
-      panel_to_global<SS_D>(R1C, SS_PSTR, L, w.ca, SS_D, grow0, 0, tid);
-      panel_to_global<SS_D>(R0, SS_PSTR, L, w.n2.y, SS_D, grow0, 0, tid);
       SS_STAMP(18);
     }
 
@@ -281,6 +311,8 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
     acc_zero<MT>(facc);
     const Dropout drf = make_dropout(p.seed, w.site_ff, p.p_drop);
     const int nj = p.ff >> 9;
+    bf16_t* const gh = w.h;
+    const long ff = p.ff;
     auto ffn_pre = [&](const int j) {                        // hpre(j) = bf16(acc + b1): to HBM now, kept packed for the pipelined GELU
 #pragma unroll
       for (int m = 0; m < MT; m++)
@@ -317,7 +349,18 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
     };
     load_bias4(bv, w.b2, wave * SS_CPW, lg);             // linear2's bias: 2 float4 that ride through the chunk loop (issued here, ahead of the stream)
     acc_zero<MT>(acc);
-    wave_gemm<MT>(acc, FIN + aoff, SS_PSTR, 0, 8, ws, b0, b1);
+    // linear1(0) carries the copies the block in front of it left behind: a2 (R1C) and x2 (R0) of a decoder layer, a and x1 of an encoder
+    // layer.  None of these slots is written before the chunk loop's first barrier (chunk 0's activation goes to HP0 = R1B / R0).
+    if constexpr (CROSS) {
+      bf16_t* const gca = w.ca; bf16_t* const gx2 = w.n2.y;
+      wave_gemm8_cb<MT>(acc, FIN + aoff, SS_PSTR, ws, b0, b1, [&](auto K) {
+        constexpr int k = decltype(K)::value;
+        panel_to_global_slice<SS_D, k, 0, IT1, 2 * IT1>(R1C, SS_PSTR, L, gca, SS_D, grow0, 0, tid);
+        panel_to_global_slice<SS_D, k, IT1, IT1, 2 * IT1>(R0, SS_PSTR, L, gx2, SS_D, grow0, 0, tid);
+      });
+    } else {
+      wave_gemm8_cb<MT>(acc, FIN + aoff, SS_PSTR, ws, b0, b1, copy_a_x1);
+    }
     ffn_pre(0);
     SS_STAMP(20);
     for (int j = 0; j < nj; j++) {
@@ -330,9 +373,10 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
       SS_STAMP(21 + 4 * j);
       ss_barrier();
       bf16_t* HP = (j & 1) ? HP1 : HP0;
-      panel_to_global<SS_D>(HP, SS_PSTR, L, w.h, p.ff, grow0, j * 512, tid);
       SS_STAMP(22 + 4 * j);
-      wave_gemm<MT>(facc, HP + aoff, SS_PSTR, 0, 8, ws, b0, b1);
+      wave_gemm8_cb<MT>(facc, HP + aoff, SS_PSTR, ws, b0, b1, [&](auto K) {      // the K slice that reads chunk j carries its copy
+        panel_to_global_slice<SS_D, decltype(K)::value, 0, IT1, IT1>(HP, SS_PSTR, L, gh, ff, grow0, j * 512, tid);
+      });
       if (j + 1 < nj) ffn_pre(j + 1);
       SS_STAMP(23 + 4 * j);
     }
@@ -343,13 +387,13 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
         for (int t = 0; t < SS_TPW; t++) res[m][t] = *reinterpret_cast<const BV4*>(FIN + (m * 16 + li) * SS_PSTR + ecol + t * 16);
       ss_barrier();                                        // the last chunk's copy and linear2 reads are done: the activation buffers become y / y2
       const Dropout dr = make_dropout(p.seed, w.site_n3, p.p_drop);
-      const SsNorm nfl = p.nf;                             // (a pointer into the by-value argument would put all of it into scratch)
-      epi_ln<MT>(facc, bv, res, nrm(w.n3), fin ? &nfl : nullptr, dr, grow0, L, FP, YP, Y2P, red, wave, li, lg);
+      epi_ln<MT>(facc, bv, res, nrm(w.n3), nrm(kp->nf), fin, dr, grow0, L, FP, YP, Y2P, red, wave, li, lg);
       SS_STAMP(40);
     }
     ss_barrier();
     panel_to_global<SS_D>(FP, SS_PSTR, L, w.f, SS_D, grow0, 0, tid);
-    panel_to_global<SS_D>(YP, SS_PSTR, L, w.n3.y, SS_D, grow0, 0, tid);
+    // y is the next layer's x: it stays in R0 untouched through that layer's first q | k | v block, which carries its copy
+    if (l + 1 == p.nl) panel_to_global<SS_D>(YP, SS_PSTR, L, w.n3.y, SS_D, grow0, 0, tid);
     if (fin) panel_to_global<SS_D>(Y2P, SS_PSTR, L, p.nf.y, SS_D, grow0, 0, tid);
     SS_STAMP(41);
     // the next layer's x is YP = R0 (rows >= L: finite LayerNorm outputs of finite rows)

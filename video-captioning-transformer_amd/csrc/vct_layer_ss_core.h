@@ -180,6 +180,36 @@ __device__ __forceinline__ void panel_to_global(const bf16_t* panel, const int p
 #endif
   }
 }
+// The same copy cut into its SS_NT-vector iterations (same thread -> vector map, so the same 1-KiB wave stores), for the forward's saved
+// tensors: nothing later in the forward waits for them, so the K steps of the NEXT product carry them (wave_gemm8_cb) beside its
+// weight stream.  A list of copies with TOT iterations in all is spread evenly over the 8 K steps; this copy holds [OFF, OFF + NIT) of it,
+// and slice K issues what falls on K step K.  The LDS reads of a slice are complete at the next ss_barrier (lgkmcnt(0)): the panel may
+// change its role behind the first barrier after the carrying product, not before.
+__host__ __device__ constexpr int ss_copy_its(const int rows_alloc, const int ncols) { return (rows_alloc * (ncols / 8) + SS_NT - 1) / SS_NT; }
+template <int NCOLS, int K, int OFF, int NIT, int TOT>
+__device__ __forceinline__ void panel_to_global_slice(const bf16_t* panel, const int pstr, const int rows, bf16_t* g, const long ld,
+                                                      const long row0, const int col0, const int tid) {
+  static_assert(TOT >= OFF + NIT && (TOT - 1) * 8 / TOT <= 7, "copy list");
+  constexpr int vpr = NCOLS / 8;
+  static_for<NIT>([&](auto I) {
+    constexpr int it = decltype(I)::value;
+    if constexpr ((OFF + it) * 8 / TOT == K) {
+      // opaque: the row / column of a vector depends on the thread index alone, and left visible every copy's addresses are computed
+      // once per layer and kept alive (spilled) from there to their K step
+      int tv = tid;
+      asm volatile("" : "+v"(tv));
+      const int v = tv + it * SS_NT;
+      if (v < rows * vpr) {
+        const int r = v / vpr, c = (v - r * vpr) * 8;
+#if SS_STREAM_STORES
+        store_stream16(g + (row0 + r) * ld + col0 + c, *reinterpret_cast<const stream_u32x4*>(panel + r * pstr + c));
+#else
+        *reinterpret_cast<BV8s*>(g + (row0 + r) * ld + col0 + c) = *reinterpret_cast<const BV8s*>(panel + r * pstr + c);
+#endif
+      }
+    }
+  });
+}
 // global rows -> panel (rows >= L zero-filled up to `alloc`)
 __device__ __forceinline__ void global_to_panel(bf16_t* panel, const int pstr, const int L, const int alloc, const bf16_t* g, const long ld,
                                                 const long row0, const int tid) {
@@ -222,9 +252,12 @@ __device__ __forceinline__ void epi_store(const f32x4 (&acc)[MT][SS_TPW], const 
 // residual + dropout + LayerNorm (+ second LayerNorm) epilogue of out_proj / linear2 (what vct_add_ln_fwd / vct_add_ln_ln_fwd compute):
 //   a = bf16(acc + bias) -> panel AP;  s = a * dropmask + res;  y = LN(s) -> panel YP;  [y2 = LN2(bf16 y) -> panel Y2P]
 // res: 4 bf16 per (m, t) in registers.  Row statistics: this wave's 64 columns -> 4-lane-group shuffle -> LDS partials of the 8 waves.
-template <int MT>
-__device__ __forceinline__ void epi_ln(f32x4 (&acc)[MT][SS_TPW], const float4 (&bv)[SS_TPW], const BV4 (&res)[MT][SS_TPW], const SsNorm& n, const SsNorm* n2,
-                                       const Dropout& dr, const long grow0, const int L, bf16_t* AP, bf16_t* YP, bf16_t* Y2P, float* red,
+// The norms come BY VALUE (has2: n2 is present): behind a pointer or a reference the structs live in private memory (scratch).
+// AP_LATE: the stores to AP wait (in registers) for the first barrier of the statistics -- for callers whose other waves may still be
+// reading AP's slot in its old role while this wave is already here (the deferred copies under the product in front of this epilogue).
+template <int MT, bool AP_LATE = false>
+__device__ __forceinline__ void epi_ln(f32x4 (&acc)[MT][SS_TPW], const float4 (&bv)[SS_TPW], const BV4 (&res)[MT][SS_TPW], const SsNorm n, const SsNorm n2,
+                                       const bool has2, const Dropout& dr, const long grow0, const int L, bf16_t* AP, bf16_t* YP, bf16_t* Y2P, float* red,
                                        const int wave, const int li_in, const int lg_in) {
   // lane indices behind an opaque barrier: otherwise the address / counter arithmetic shared by the layer's three LayerNorm
   // epilogues is computed once and kept alive (spilled) from the first to the last of them
@@ -236,6 +269,7 @@ __device__ __forceinline__ void epi_ln(f32x4 (&acc)[MT][SS_TPW], const float4 (&
   float4 gm[SS_TPW], bt[SS_TPW];
   load_gb(gm, bt, n, colw);
   float part[MT];
+  BV4 avl[AP_LATE ? MT : 1][SS_TPW];
 #pragma unroll
   for (int m = 0; m < MT; m++) {
     part[m] = 0.0f;
@@ -253,7 +287,8 @@ __device__ __forceinline__ void epi_ln(f32x4 (&acc)[MT][SS_TPW], const float4 (&
         acc[m][t][r] = s;
         part[m] += s;
       }
-      *reinterpret_cast<BV4*>(AP + (m * 16 + li) * SS_PSTR + colw + t * 16) = av;
+      if constexpr (AP_LATE) avl[m][t] = av;
+      else *reinterpret_cast<BV4*>(AP + (m * 16 + li) * SS_PSTR + colw + t * 16) = av;
     }
     part[m] = red4_sum(part[m]);
   }
@@ -262,12 +297,18 @@ __device__ __forceinline__ void epi_ln(f32x4 (&acc)[MT][SS_TPW], const float4 (&
   // waves are aligned by the first, the extra in-register pass does.)
   float* red0 = red;                  // [8][32]
   float* red1 = red + SS_NW * 32;
-  auto stats = [&](float (&mean)[MT], float (&rstd)[MT]) {
+  auto stats = [&](float (&mean)[MT], float (&rstd)[MT], auto FIRST) {
     if (lg == 0) {
 #pragma unroll
       for (int m = 0; m < MT; m++) red0[wave * 32 + m * 16 + li] = part[m];
     }
     ss_barrier();
+    if constexpr (AP_LATE && decltype(FIRST)::value) {     // every wave is past its product (and the copies it carried): AP's slot is free
+#pragma unroll
+      for (int m = 0; m < MT; m++)
+#pragma unroll
+        for (int t = 0; t < SS_TPW; t++) *reinterpret_cast<BV4*>(AP + (m * 16 + li) * SS_PSTR + colw + t * 16) = avl[m][t];
+    }
     float sq[MT];
 #pragma unroll
     for (int m = 0; m < MT; m++) {
@@ -296,7 +337,7 @@ __device__ __forceinline__ void epi_ln(f32x4 (&acc)[MT][SS_TPW], const float4 (&
     }
   };
   float mean[MT], rstd[MT];
-  stats(mean, rstd);
+  stats(mean, rstd, std::true_type{});
   if (wave == 0 && lg == 0) {
 #pragma unroll
     for (int m = 0; m < MT; m++)
@@ -319,17 +360,17 @@ __device__ __forceinline__ void epi_ln(f32x4 (&acc)[MT][SS_TPW], const float4 (&
     }
     part[m] = red4_sum(part[m]);
   }
-  if (n2 != nullptr) {
+  if (has2) {
 #pragma unroll
     for (int t = 0; t < SS_TPW; t++) {
-      gm[t] = *reinterpret_cast<const float4*>(n2->g + colw + t * 16);
-      bt[t] = *reinterpret_cast<const float4*>(n2->b + colw + t * 16);
+      gm[t] = *reinterpret_cast<const float4*>(n2.g + colw + t * 16);
+      bt[t] = *reinterpret_cast<const float4*>(n2.b + colw + t * 16);
     }
-    stats(mean, rstd);
+    stats(mean, rstd, std::false_type{});
     if (wave == 0 && lg == 0) {
 #pragma unroll
       for (int m = 0; m < MT; m++)
-        if (m * 16 + li < L) { n2->mean[grow0 + m * 16 + li] = mean[m]; n2->rstd[grow0 + m * 16 + li] = rstd[m]; }
+        if (m * 16 + li < L) { n2.mean[grow0 + m * 16 + li] = mean[m]; n2.rstd[grow0 + m * 16 + li] = rstd[m]; }
     }
 #pragma unroll
     for (int m = 0; m < MT; m++)
