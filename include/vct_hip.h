@@ -865,6 +865,33 @@ int vct_adam_step_2d(float* param, const float* grad, float* exp_avg, float* exp
                      void* shadow_t_bf16, int32_t rows, int32_t cols, int64_t ld_t, float lr, float beta1, float beta2,
                      float eps, float weight_decay, int32_t* step_dev, const float* hyper_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Gradient clipping over the flat fp32 gradient buffer (csrc/vct_grad_clip.hip).
+ * replaces: torch.nn.utils.clip_grad_norm_ (L2, error_if_nonfinite = False) / torch.nn.utils.clip_grad_value_ on the parameters an
+ * optimizer owns.  No reference counterpart in train.py (the reference never clips); the arithmetic is torch's:
+ *   norm = || (||g_1||, ..., ||g_n||) ||_2, coef = clamp(max_norm / (norm + 1e-6), max = 1), g_i *= coef   |   g_i.clamp_(-v, v).
+ * segs_dev: DEVICE table of nseg flat-element segments [begin, end), sorted and disjoint, one per parameter; begin a multiple of
+ * 4, end arbitrary (the last elements of a segment are handled one by one: no reliance on padding, nothing outside a segment is read
+ * or written); blk0 = number of 4096-element workgroups of all earlier segments (as vct_adam_range), total_blocks = those of all.
+ * vct_grad_sqnorm (two launches, no atomics, two runs give the same bits): every element is widened to fp64 and accumulated by
+ * fp64 FMAs, one partial per workgroup in a fixed order; then one workgroup adds the partials of each segment (a wave per segment,
+ * fixed stride, fixed shuffle tree) and the segment sums in ascending order.
+ *   partials : DEVICE fp64 [total_blocks + nseg] scratch (the workgroup partials, then the segment sums), 16-byte aligned
+ *   seg_norm : DEVICE fp32 [nseg] <- (float)sqrt(sum_i)
+ *   clip_dev : DEVICE fp32 [2] = {max_norm, max_value}; read by the kernels, so recordings follow a change
+ *   state    : DEVICE fp32 [4] <- {norm = (float)sqrt(sum of the segment sums), coef, 0, 0} with, in fp32,
+ *              q = max_norm / (norm + 1e-6f), coef = q > 1 ? 1 : q (a NaN stays, as with torch.clamp).
+ * vct_grad_clip_apply (one launch, plain vector stores): mode 0 multiplies every element of every segment by state[1] -- a
+ * workgroup that reads exactly 1.0f leaves without touching memory, which is bitwise the multiplication; mode 1 clamps to
+ * [-clip_dev[1], clip_dev[1]] like torch.clamp (NaN stays NaN, -0.0 stays -0.0; state may be NULL).
+ * Null pointers: VCT_E_ARG; nseg <= 0 or total_blocks <= 0: VCT_E_SHAPE; grad / partials / segs_dev not 16-byte aligned: VCT_E_ALIGN.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct vct_grad_seg { int64_t begin, end; int32_t blk0, reserved; } vct_grad_seg;
+int vct_grad_sqnorm(const float* grad, const vct_grad_seg* segs_dev, int32_t nseg, int32_t total_blocks, double* partials,
+                    float* seg_norm, const float* clip_dev, float* state, void* stream);
+int vct_grad_clip_apply(float* grad, const vct_grad_seg* segs_dev, int32_t nseg, int32_t total_blocks, int32_t mode,
+                        const float* clip_dev, const float* state, void* stream);
+
 /* elementwise helpers ------------------------------------------------------------------------ */
 /* dst[i] = (dst_dtype) src[i], n elements (fp32 <-> bf16 parameter / feature casts) */
 int vct_cast(int src_dtype, int dst_dtype, const void* src, void* dst, int64_t n, void* stream);

@@ -38,6 +38,12 @@ class AdamRows(C.Structure):
     _fields_ = [("origin", i64), ("row_len", i32), ("nrows", i32), ("live", vp)]
 
 
+class GradSeg(C.Structure):
+    """include/vct_hip.h, vct_grad_seg: one parameter's elements of the flat gradient buffer (gradient clipping)."""
+    _c_name_ = "vct_grad_seg"
+    _fields_ = [("begin", i64), ("end", i64), ("blk0", i32), ("reserved", i32)]
+
+
 class GemmDesc(C.Structure):
     _c_name_ = "vct_gemm_desc"
     _fields_ = [("dtype", i32), ("out_dtype", i32), ("ta", i32), ("tb", i32), ("M", i32), ("N", i32), ("K", i32),
@@ -354,6 +360,8 @@ _SIGS = {
     "vct_adam_step_ranges": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, i32, vp]),
     "vct_adam_step_ranges_rows": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, i32, vp, vp]),
     "vct_adam_step_2d": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i64, f32, f32, f32, f32, f32, vp, vp, vp]),
+    "vct_grad_sqnorm": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp]),
+    "vct_grad_clip_apply": (C.c_int, [vp, vp, i32, i32, i32, vp, vp, vp]),
     "vct_cmdlist_create": (C.c_int, [C.POINTER(vp)]),
     "vct_cmdlist_destroy": (C.c_int, [vp]),
     "vct_cmdlist_begin": (C.c_int, [vp, vp]),

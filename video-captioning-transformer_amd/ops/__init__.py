@@ -7,6 +7,7 @@ every name the package exposes."""
 from .. import _lib as L        # ops.L.GemmAdam, ops.L.GEMM_GROUP_MAX: the engine and the trainer reach the mirror through here
 from ._common import Drop
 from .attention import attn_bwd, attn_fwd, attn_weights
+from .clip import grad_clip_apply, grad_segments_table, grad_sqnorm, grad_sqnorm_scratch
 from .decoding import (beam_reorder, beam_select, beam_select_workspace_bytes, decode_block, decode_block_supported, decode_gemv,
                        decode_linear, decode_ln2, greedy_select, logit_controls, sample_select, sample_select_workspace_bytes)
 from .elementwise import advance_seed, argmax_rows, axpby, cast, gather_pad_rows, scale, transpose, warm

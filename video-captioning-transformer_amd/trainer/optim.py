@@ -5,6 +5,7 @@ import os
 import torch
 
 from .. import ops
+from .clip import KEYS as CLIP_KEYS, check_clip_settings
 
 
 def owned_range(model, task):
@@ -23,13 +24,17 @@ def owned_range(model, task):
 class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam / AdamW semantics (reference train.py:24-31) as ONE kernel over the model's flat
     fp32 parameter buffer, which also rewrites the bf16 shadow the GEMMs read.  `param_groups[0]['lr']`
-    is honoured every step, so torch LR schedulers work unchanged."""
+    is honoured every step, so torch LR schedulers work unchanged.
+    max_grad_norm / clip_grad_value: gradient clipping by global norm or by value (one of them; trainer/clip.py).  They are kept
+    in `param_groups[0]` (only when set), so state_dict / load_state_dict and checkpoint.save_training_state carry them; the
+    launches belong to the step executor (CaptionTrainer), which reads them there before every step."""
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, clip_grad_value=None):
         self.model = model
         flat = torch.nn.Parameter(model.flat_params, requires_grad=True)
         flat.grad = model.flat_grads
         super().__init__([flat], dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        set_clip_settings(self, max_grad_norm, clip_grad_value)
         ps = model._ps
         self.exp_avg = torch.zeros_like(ps.flat)
         self.exp_avg_sq = torch.zeros_like(ps.flat)
@@ -313,10 +318,19 @@ class FusedAdam(torch.optim.Optimizer):
         self.sync_hyper()
 
 
+def set_clip_settings(optimizer, max_grad_norm=None, clip_grad_value=None):
+    """Validate the clipping settings and write those that are set into optimizer.param_groups[0] (any optimizer kind)."""
+    check_clip_settings(max_grad_norm, clip_grad_value)
+    for key, v in zip(CLIP_KEYS, (max_grad_norm, clip_grad_value)):
+        if v is not None:
+            optimizer.param_groups[0][key] = float(v)
+
+
 def build_optimizer(train_cfg: dict, model):
     """Optimizer + scheduler factory with the reference's config surface (train.py:20-49).  The
     optimizer sees ONE parameter -- the flat fp32 buffer, whose .grad is the flat gradient buffer --
-    so Adam is a single fused multi-tensor kernel instead of ~70 small ones."""
+    so Adam is a single fused multi-tensor kernel instead of ~70 small ones.
+    Beyond the reference: the optional train.optimizer.max_grad_norm / clip_grad_value (gradient clipping, trainer/clip.py)."""
     oc = train_cfg["optimizer"]
 
     def flat():      # what a torch optimizer steps (FusedAdam makes its own)
@@ -334,6 +348,7 @@ def build_optimizer(train_cfg: dict, model):
         opt = torch.optim.SGD(flat(), lr=oc["learning_rate"], momentum=oc["momentum"])
     else:
         raise ValueError("Do not support optimizer: {}".format(oc["name"]))
+    set_clip_settings(opt, oc.get("max_grad_norm"), oc.get("clip_grad_value"))
     sched = None
     sc = oc.get("lr_scheduler")
     if sc:

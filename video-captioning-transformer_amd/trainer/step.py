@@ -9,8 +9,9 @@ import torch.distributed as dist
 from .. import ops
 from ..engine import first_input, stage_inputs, static_inputs
 from ..utils import capture_graph
+from .clip import GradClipper, clip_settings_of
 from .exchange import GradExchange, ShardedExchange
-from .optim import FusedAdam
+from .optim import FusedAdam, owned_range
 
 
 class CaptionTrainer:
@@ -32,7 +33,10 @@ class CaptionTrainer:
         """keep_weight_grads: on the single-GPU bf16 FusedAdam path the 2-D weights are stepped inside their weight-gradient GEMMs and
         their gradients are NOT stored (model.grads_valid is False after a step; the reference leaves valid .grad after backward,
         train.py:125).  True stores them as well (for clipping, logging, hooks; costs the 4 B per parameter the fusion saved);
-        None: the VCT_FUSE_ADAM_KEEP_GRAD environment switch (default off)."""
+        None: the VCT_FUSE_ADAM_KEEP_GRAD environment switch (default off).
+        Clipping needs none of this: set max_grad_norm / clip_grad_value on the optimizer (FusedAdam(..., max_grad_norm=...),
+        train.optimizer.max_grad_norm, or param_groups[0]) and the step clips on the device (trainer/clip.py); the fusion is then off
+        and every gradient is stored.  After such a step: last_grad_norm, last_clip_coef, grad_norms()."""
         self.model, self.opt, self.ex = model, optimizer, exchange
         fused = self._fused = isinstance(optimizer, FusedAdam)
         # the task the optimizer was built for (FusedAdam remembers model.f_type; a torch optimizer's filter(requires_grad) followed it)
@@ -67,8 +71,55 @@ class CaptionTrainer:
         # enable_dw_fusion); the hook is installed only WHILE this trainer enqueues a step (a plain loss.backward() outside it must
         # keep producing gradients and nothing else)
         # (match / cross: off -- cross scales the gradients before they are consumed, match gains nothing worth the risk)
-        self.fuse_adam = bool(single and optimizer.fuse_dw_default and self.task == "caption"
-                              and model._ps.compute_dtype == torch.bfloat16 and model.flat_grads.is_cuda)
+        self._fuse_base = self.fuse_adam = bool(single and optimizer.fuse_dw_default and self.task == "caption"
+                                                and model._ps.compute_dtype == torch.bfloat16 and model.flat_grads.is_cuda)
+        # gradient clipping (optimizer.param_groups[0]: max_grad_norm / clip_grad_value; trainer/clip.py).  Off unless one is set: no
+        # launch is added or moved.  On: the norm needs every gradient in memory before any parameter is stepped, so the optimizer
+        # leaves the weight-gradient GEMMs (fuse_adam off) and the caption step takes the plain branch -- backward with both streams
+        # joined, the clipper's two or three launches, the optimizer.
+        self.clipper = None
+        self._clip_mode = None
+        self._sync_clip()
+
+    # ---- gradient clipping -------------------------------------------------------------------------------------------------------------
+    def _sync_clip(self):
+        """Follow the clipping settings of optimizer.param_groups[0] (a scheduler, load_state_dict or the user may have written
+        them): validate, switch the step's shape when clipping was turned on or off (recordings are dropped: they bake the launches),
+        upload the thresholds when they changed.  Host-only otherwise; called before every step, outside any capture."""
+        mode, max_norm, max_value = clip_settings_of(self.opt)
+        if mode != self._clip_mode:
+            if mode is not None and self.ex is not None and self.ex.active:
+                raise NotImplementedError("gradient clipping with an active gradient exchange is not built: the sharded path steps "
+                                          "each bucket before the global norm exists")
+            if mode is not None and self.clipper is None:
+                begin, end = (self.opt.begin, self.opt.end) if self._fused else owned_range(self.model, self.task)
+                self.clipper = GradClipper(self.model, begin, end)
+            self._clip_mode = mode
+            self.fuse_adam = self._fuse_base and mode is None
+            self.drop_recordings()
+        if mode is not None:
+            self.clipper.sync(max_norm, max_value)
+
+    def _clip(self):
+        """The clipper's launches on the current stream, between the backward (every stream joined) and the optimizer."""
+        if self._clip_mode is not None:
+            self.clipper.enqueue()
+
+    @property
+    def last_grad_norm(self):
+        """0-dim device fp32: the global L2 norm of the last step's gradients BEFORE clipping (what clip_grad_norm_ returns); a view
+        of the clipper's state, rewritten by the next step.  None unless max_grad_norm is set."""
+        return self.clipper.state[0] if self._clip_mode == "norm" else None
+
+    @property
+    def last_clip_coef(self):
+        """0-dim device fp32: the factor the last step's gradients were multiplied by (1 = not clipped).  None unless max_grad_norm is set."""
+        return self.clipper.state[1] if self._clip_mode == "norm" else None
+
+    def grad_norms(self):
+        """(parameter names, device fp32 [n]): the L2 norm of every parameter's gradient before clipping -- a by-product of the
+        last step's norm pass.  None unless max_grad_norm is set."""
+        return (list(self.clipper.names), self.clipper.seg_norm) if self._clip_mode == "norm" else None
 
     def _check_task(self, task):
         """The matching task runs on the eager executor of one process: refuse the rest loudly, before any device work."""
@@ -95,7 +146,8 @@ class CaptionTrainer:
         if self.task == "match":
             out = m.train_step_kernels_match(feats, mask, text_feats)
         else:
-            out = m.train_step_kernels_cross(feats, mask, ids, text_feats)
+            out = m.train_step_kernels_cross(feats, mask, ids, text_feats)      # (the loss_beta mix of the gradients is part of it)
+        self._clip()
         self.opt.step()
         if m.training and m.video_encoder.cfg["dropout"] > 0:
             ops.advance_seed(m._seed)
@@ -135,6 +187,7 @@ class CaptionTrainer:
         them when you need the numbers (scst_epoch does it once per epoch).  max_len above 65 is a ValueError there, before any
         launch (the reward kernel takes the start column + 64 tokens)."""
         self._check_scst(num_samples, baseline)
+        self._sync_clip()
         if getattr(reward_fn, "on_device", False):
             return self._scst_step_device(feats, mask, reward_fn, vids, int(num_samples), baseline, max_len, temperature, top_k, top_p,
                                           seed)
@@ -162,6 +215,7 @@ class CaptionTrainer:
             base = r - adv
         seq_w = torch.from_numpy(np.ascontiguousarray(adv.reshape(-1))).to(ids.device)
         loss = m.train_step_kernels_scst(feats, mask, ids.view(B * N, -1), seq_w, N)
+        self._clip()
         self.opt.step()
         if m.training and m.video_encoder.cfg["dropout"] > 0:
             ops.advance_seed(m._seed)
@@ -195,6 +249,7 @@ class CaptionTrainer:
         base = reward_fn(greedy.view(B, 1, -1), vids).view(B) if greedy is not None else None
         seq_w, _, means = ops.scst_advantages(r.contiguous(), base)
         loss = m.train_step_kernels_scst(feats, mask, ids.view(B * N, -1), seq_w, N)
+        self._clip()
         self.opt.step()
         if m.training and m.video_encoder.cfg["dropout"] > 0:
             ops.advance_seed(m._seed)
@@ -235,6 +290,11 @@ class CaptionTrainer:
             else:
                 self.ex.finish()
                 self.opt.step()
+        elif self._clip_mode is not None:
+            # clipping: the whole backward with both streams joined, the norm over every gradient, then the optimizer
+            loss = m.train_step_kernels(feats, mask, ids)
+            self._clip()
+            self.opt.step()
         elif fused and self.overlap_adam and first_input(feats).is_cuda:
             # single GPU: Adam on each gradient bucket the moment backward completes it, on the side stream, so the
             # 1.4 GB optimizer pass hides under the rest of backward instead of trailing it
@@ -363,6 +423,7 @@ class CaptionTrainer:
             raise ValueError(f"model.mode({task!r}) but the optimizer was built for {self.task!r}: build the optimizer after model.mode(task)")
         if self._fused:
             self.opt.sync_hyper()
+        self._sync_clip()
         if self.fuse_adam:
             # the embedding's live-row table exists and is true before the step is enqueued, recorded or replayed (host-only check
             # unless an optimizer state was loaded or a dense pass ran over the table since the last step)
