@@ -561,6 +561,25 @@ int vct_sce_loss(int dtype, int N, int S, int V, const void* logits, int64_t ldl
                  int64_t ld_dl, float* row_ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * vct_sce_loss with label smoothing on its CE term, plus the un-smoothed NLL and the token accuracy (csrc/vct_sce_ls.hip).
+ * replaces: nn.CrossEntropyLoss(ignore_index, label_smoothing) at alpha == 1; the reference's SCELoss has no smoothing -- with
+ * alpha < 1 the CE term is smoothed and the RCE term is vct_sce_loss's, unchanged.
+ *   eps = smoothing in [0, 1);  row n valid when its label y != pad_id;  count = number of valid rows;  lse, p over the V columns
+ *   nll_n = lse - x[y];  smooth_n = lse - (1/V) sum_{j<V} x[j];  ce_n = (1 - eps) nll_n + eps smooth_n  (0 on pad rows)
+ *   loss_out[0] = alpha * sum ce_n / count + (1 - alpha) * L_rce               (L_rce: vct_sce_loss's, mean over all N rows)
+ *   dlogits[n, j] = (alpha / count) (p_j - (1 - eps) [j == y] - eps / V) [valid] + vct_sce_loss's RCE part; columns V..ld_dl-1 = 0
+ *   stats_out[0] = sum over valid n of nll_n / count;  stats_out[1] = #{valid n: x[y] == max_j x[j]} / count (a tie with the
+ *   maximum counts as a hit; a label outside the vocabulary as a miss)                              (fp32 [2] or NULL)
+ * smoothing == 0 gives vct_sce_loss's loss_out and dlogits bit for bit.  smoothing outside [0, 1) or NaN: VCT_E_ARG, nothing
+ * launched.  Limits, alignment, aliasing (dlogits may be logits; NULL = forward only), the out-of-vocabulary label (column 0; NaN
+ * loss and NaN stats_out[0]), count == 0 and the other return codes are vct_sce_loss's.  row_ws fp32 [4*N + 2] scratch.  Two calls
+ * are bitwise equal (fixed-order single-workgroup count and finalise, no float atomics).
+ * --------------------------------------------------------------------------------------------- */
+int vct_sce_loss_ls(int dtype, int N, int S, int V, const void* logits, int64_t ldl, const int64_t* labels,
+                    int64_t label_batch_stride, int64_t pad_id, float alpha, float smoothing, float* loss_out,
+                    float* stats_out, void* dlogits, int64_t ld_dl, float* row_ws, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Sequence-weighted cross-entropy for self-critical sequence training (csrc/vct_wce_loss.hip): vct_sce_loss at alpha = 1 with
  * one weight (the advantage) per sequence.  The reference has no policy-gradient stage; the semantics are DESIGN.md's.
  *   row n belongs to sequence b = n / S, label = labels[b*label_batch_stride + n % S], valid when label != pad_id;

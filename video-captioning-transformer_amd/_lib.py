@@ -331,6 +331,7 @@ _SIGS = {
     "vct_embed_bwd_live": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, i64, vp, vp, vp, i64, C.c_int, vp, u32, f32, vp, vp]),
     "vct_embed_live_rebuild": (C.c_int, [i32, i32, vp, vp, vp, vp, vp]),
     "vct_sce_loss": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, i64, f32, vp, vp, i64, vp, vp]),
+    "vct_sce_loss_ls": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, i64, f32, f32, vp, vp, vp, i64, vp, vp]),
     "vct_wce_loss": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, i64, vp, vp, vp, vp, i64, vp, vp]),
     "vct_group_sum": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "vct_cider_d": (C.c_int, [C.POINTER(CiderDesc), vp]),

@@ -28,6 +28,7 @@ class DecoderEngine(_StackBase):
     block_decode = os.environ.get("VCT_BLOCK_DECODE", "1") != "0"   # A/B switch: 3 launches per layer at batch 1 (bf16)
     small_batch_decode = True       # A/B switch: weight-streaming GEMV step for batch <= 4
     attn_maps = False               # set per ENGINE by CapDecoder(custom_decoder_type=...): every forward also leaves the cross-attention maps
+    loss_stats = False              # set per ENGINE by CapDecoder.loss_stats: the caption loss also leaves (NLL, token accuracy) at label_smoothing 0
 
     def __init__(self, ps, prefix, cfg, seed, pos_buffer: torch.Tensor):
         super().__init__(ps, prefix, cfg, seed)
@@ -41,6 +42,7 @@ class DecoderEngine(_StackBase):
         self.lps, self.tags, self.sites = [f"decoder.layers.{l}." for l in ls], [f"L{l}." for l in ls], [DEC_SITE + 16 * l for l in ls]
         self._wgt = None     # W_g^T of the current forward when the vocabulary dX runs in its NT form (gen_dx_nt), else None
         self.last_attn_maps = None     # attn_maps: fp32 [B, S-1, Te] per layer of the last forward (views of static buffers)
+        self.last_loss_stats = None    # fp32 [2] (un-smoothed NLL, token accuracy) of the last forward that ran ops.sce_loss_ls, else None
 
     def _ws_grew(self):
         self.ps.ctx.generation += 1      # recordings that baked the outgrown id workspace are dropped by their owners
@@ -128,7 +130,13 @@ class DecoderEngine(_StackBase):
         (ops.wce_loss) in place of the SCE loss.  The RCE term and sce_loss_alpha are IGNORED on this path: the policy gradient of
         an expected reward is -A * grad log p and nothing else.  score=True: forward only (no logits gradient is written; backward()
         must not follow), unit weights.  Both leave the per-token log-probabilities fp32 [B*(S-1)] (0 on pad rows) in the
-        buffer set as "tok_logp"."""
+        buffer set as "tok_logp".
+
+        cfg["label_smoothing"] = eps > 0 (or loss_stats at eps = 0): the SCE loss with its CE term smoothed (ops.sce_loss_ls), which
+        also leaves (un-smoothed NLL, token accuracy) fp32 [2] in the buffer set as "loss_stats" -- a recorded launch list or a
+        captured graph rewrites it on every replay.  eps is a launch scalar like sce_loss_alpha: a recording keeps the value it was
+        made with.  With neither, the call is the ops.sce_loss call it always was.  The seq_w / score paths (ops.wce_loss) IGNORE
+        eps as they ignore sce_loss_alpha: a policy gradient is not regularised towards the uniform distribution."""
         pad = self.cfg["pad_id"]
         S = ids.shape[1]
         Sd, M = S - 1, Bn * (S - 1)
@@ -154,9 +162,15 @@ class DecoderEngine(_StackBase):
         loss = b.get("loss", (1,), torch.float32)
         dlogits = None if score else (b.get("dlogits", (M, self.Vp), self.dt) if want_logits else logits)
         ops.tap("loss", 0)
+        eps = float(self.cfg.get("label_smoothing", 0.0))
+        self.last_loss_stats = None
         if seq_w is not None or score:
             ops.wce_loss(logits, self.V, ids[:, 1:], Sd, pad, seq_w, loss, dlogits, b.get("row_ws", (2 * M + 2,), torch.float32),
                          tok_logp=b.get("tok_logp", (M,), torch.float32))
+        elif eps > 0.0 or self.loss_stats:
+            stats = self.last_loss_stats = b.get("loss_stats", (2,), torch.float32)
+            ops.sce_loss_ls(logits, self.V, ids[:, 1:], Sd, pad, self.cfg["sce_loss_alpha"], eps, loss, dlogits,
+                            b.get("row_ws_ls", (4 * M + 2,), torch.float32), stats=stats)
         else:
             ops.sce_loss(logits, self.V, ids[:, 1:], Sd, pad, self.cfg["sce_loss_alpha"], loss, dlogits,
                          b.get("row_ws", (2 * M + 2,), torch.float32))

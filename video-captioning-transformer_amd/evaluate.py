@@ -136,17 +136,34 @@ def eval_epoch(model, dataloader, max_len: int = 30, beam_size: Optional[int] = 
 
 
 @torch.no_grad()
-def val_epoch(model, dataloader, mode: str = "caption", text_feats_fn=None):
+def val_epoch(model, dataloader, mode: str = "caption", text_feats_fn=None, with_stats: bool = False):
     """train.py:150-167: mean loss over the loader, model in eval mode -- teacher-forced for 'caption' (a float), the contrastive
     loss for 'match' (a float), (loss, cap_loss, match_loss) for 'cross'.  text_feats_fn(captions, vids) -> fp32
-    [B, text_encoder.dim] (match / cross); without it model.text_encoder(captions).  One device->host sync per epoch."""
+    [B, text_encoder.dim] (match / cross); without it model.text_encoder(captions).  One device->host sync per epoch.
+    With caption_decoder.label_smoothing > 0 the caption loss is the SMOOTHED criterion, as the reference's loop would return it.
+    with_stats=True ('caption' / 'cross'): returns (that value, {"nll": ..., "token_acc": ...}) -- the epoch means (over batches, like
+    the loss) of the un-smoothed NLL per token and of the token accuracy, read in the same single sync."""
     if mode not in ("caption", "match", "cross"):
         raise ValueError(f"unknown task {mode!r}")
+    if with_stats and mode == "match":
+        raise ValueError("with_stats: the match task has no caption loss")
     model.eval()
     model.mode(mode)
     model.check_task(mode)
     dev = model.device
+    if with_stats:
+        was = model.cap_decoder.loss_stats
+        model.cap_decoder.loss_stats = True
+        try:
+            return _val_epoch(model, dataloader, mode, text_feats_fn, dev, True)
+        finally:
+            model.cap_decoder.loss_stats = was
+    return _val_epoch(model, dataloader, mode, text_feats_fn, dev, False)
+
+
+def _val_epoch(model, dataloader, mode, text_feats_fn, dev, with_stats):
     total, n = torch.zeros(3 if mode == "cross" else 1, device=dev), 0
+    stats = torch.zeros(2, device=dev)
     for v_feats, v_masks, captions, vids in dataloader:
         v_feats = [f.to(dev, non_blocking=True) for f in v_feats]
         v_masks = [m.to(dev, non_blocking=True) for m in v_masks]
@@ -157,10 +174,14 @@ def val_epoch(model, dataloader, mode: str = "caption", text_feats_fn=None):
             text = text.to(dev, non_blocking=True) if torch.is_tensor(text) else text
             out = model(v_feats, v_masks, captions, text_feats=text)
             total += torch.stack([o.detach() for o in out]) if mode == "cross" else out.detach().reshape(1)
+        if with_stats:
+            stats += model.cap_decoder._engine().last_loss_stats
         n += 1
-    if mode == "cross":
-        return tuple(v / max(n, 1) for v in total.tolist())
-    return float(total) / max(n, 1)
+    vals = torch.cat([total, stats]).tolist()
+    out = tuple(v / max(n, 1) for v in vals[:-2]) if mode == "cross" else vals[0] / max(n, 1)
+    if with_stats:
+        return out, {"nll": vals[-2] / max(n, 1), "token_acc": vals[-1] / max(n, 1)}
+    return out
 
 
 def _reference_ids(pre, caption) -> List[int]:

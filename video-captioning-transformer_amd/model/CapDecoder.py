@@ -9,7 +9,7 @@ import torch.nn as nn
 from ..engine import DecoderEngine, ParamSet
 from ._params import LinearParams, StackParams
 from .Embedding import PositionalEmbedding
-from .loss import SCELoss
+from .loss import SCELoss, check_label_smoothing
 
 
 class EmbeddingParams(nn.Module):
@@ -62,21 +62,30 @@ class _DecoderFn(torch.autograd.Function):
 class CapDecoder(nn.Module):
     def __init__(self, num_layers, embed_dim, nhead, dim_feedforward, dropout, vocab_size, pad_id, sce_loss_alpha: float,
                  custom_decoder_type: Optional[str] = None, activation="gelu", device=torch.device("cuda"),
-                 compute_dtype: torch.dtype = torch.bfloat16):
+                 compute_dtype: torch.dtype = torch.bfloat16, label_smoothing: float = 0.0):
+        """label_smoothing (no reference counterpart): eps in [0, 1), nn.CrossEntropyLoss(label_smoothing=eps) at sce_loss_alpha = 1;
+        below 1 the CE term of the SCE loss is smoothed and the RCE term is not.  The training loss is then no NLL: with eps > 0, or
+        with `loss_stats = True` on this module at eps = 0, every caption forward also leaves the un-smoothed NLL and the token
+        accuracy on the device (DecoderEngine.last_loss_stats; CaptionTrainer.last_nll / last_token_acc).  Self-critical training and
+        score_captions ignore eps."""
         super().__init__()
+        label_smoothing = check_label_smoothing(label_smoothing)
+        self.loss_stats = False
         # any non-None type builds the reference's VisTransformerDecoder (CapDecoder.py:17-24): the stock layers' parameters and
         # state_dict keys, plus `attn_weights` (one head-averaged cross-attention map [B, S-1, Te] per layer) after every forward
         self.custom_decoder_type = custom_decoder_type
         self.device, self.compute_dtype = device, compute_dtype
         self.cfg = dict(d=embed_dim, nhead=nhead, ff=dim_feedforward, layers=num_layers, dropout=float(dropout),
-                        activation=activation, vocab=vocab_size, pad_id=pad_id, sce_loss_alpha=float(sce_loss_alpha))
+                        activation=activation, vocab=vocab_size, pad_id=pad_id, sce_loss_alpha=float(sce_loss_alpha),
+                        label_smoothing=label_smoothing)
         self.decoder = StackParams(embed_dim, dim_feedforward, num_layers, True, device)
         self.generator = LinearParams(embed_dim, vocab_size, device)
         self.tgt_to_emb = EmbeddingParams(vocab_size, embed_dim, pad_id, device)
         self.positional_encoding = PositionalEmbedding(embed_dim, dropout=dropout, maxlen=5000, device=device)
         # kept for API parity (CapDecoder.py:28-32); the fused kernel implements both branches
-        self.loss_fn = (nn.CrossEntropyLoss(ignore_index=pad_id) if sce_loss_alpha == 1.0
-                        else SCELoss(sce_loss_alpha, 1 - sce_loss_alpha, ignore_index=pad_id, num_classes=vocab_size))
+        self.loss_fn = (nn.CrossEntropyLoss(ignore_index=pad_id, label_smoothing=label_smoothing) if sce_loss_alpha == 1.0
+                        else SCELoss(sce_loss_alpha, 1 - sce_loss_alpha, ignore_index=pad_id, num_classes=vocab_size,
+                                     label_smoothing=label_smoothing))
         self._ps: Optional[ParamSet] = None
         self._prefix, self._eng, self._seed, self._rebuild = "", None, None, None
         self._unit_loss_grad = False
@@ -98,6 +107,7 @@ class CapDecoder(nn.Module):
         if self._eng is None:
             self._eng = DecoderEngine(self._ps, self._prefix, self.cfg, self._seed, self.positional_encoding.pos_embedding)
             self._eng.attn_maps = self.custom_decoder_type is not None
+        self._eng.loss_stats = bool(self.loss_stats)
         return self._eng
 
     def _publish_attn(self, eng):

@@ -106,7 +106,8 @@ class MMT4Caption(nn.Module):
             dim_feedforward=dec_cfg["feedforward"], dropout=model_config["dropout"],
             vocab_size=self.cap_preprocessor.tokenizer.vocab_size, pad_id=self.cap_preprocessor.pad_id,
             sce_loss_alpha=dec_cfg["sce_loss_alpha"], custom_decoder_type=dec_cfg.get("layer_type", None),
-            activation=model_config["activation"], device=device, compute_dtype=self.compute_dtype)
+            activation=model_config["activation"], device=device, compute_dtype=self.compute_dtype,
+            label_smoothing=dec_cfg.get("label_smoothing", 0.0))      # optional key: absent = 0 = the reference's criterion
         enc_type = enc_cfg.get("type", "mme")
         if enc_type not in ("mme", "hmme"):
             raise NotImplementedError(f"video_encoder.type {enc_type!r} is outside the accelerated caption path ('mme' and 'hmme' are on it)")

@@ -17,7 +17,7 @@ from .frontend import (enc_frontend_bwd, enc_frontend_ex_bwd, enc_frontend_ex_fw
 from .gemms import GemmScratch, _gemm_desc, gemm, gemm_grouped, gemm_last_route, gemm_workspace_bytes
 from .layer_ss import (SS_CHUNK, layer_ss_bwd, layer_ss_bwd_desc, layer_ss_bwd_stream_chunks, layer_ss_desc, layer_ss_fwd,
                        layer_ss_stream_chunks, layer_ss_supported, ss_pack)
-from .loss import group_sum, sce_loss, wce_loss
+from .loss import group_sum, sce_loss, sce_loss_ls, wce_loss
 from .matching import match_agg_bwd, match_agg_fwd, match_loss, match_loss_workspace_bytes, retrieval_ranks, retrieval_workspace_bytes
 from .norm import add_ln_bwd, add_ln_fwd, add_ln_ln_bwd, add_ln_ln_fwd, ln_param_finalize_batched, ln_ws_rows, preln_fwd
 from .optim import adam_bump, adam_ranges_table, adam_step, adam_step_2d, adam_step_ranges

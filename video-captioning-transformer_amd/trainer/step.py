@@ -29,8 +29,11 @@ class CaptionTrainer:
     to grow (engine/params.py: StepContext.generation), because they bake device pointers."""
 
     def __init__(self, model, optimizer, exchange: Optional[GradExchange] = None, use_graph: bool = False,
-                 launch_list: Optional[bool] = None, keep_weight_grads: Optional[bool] = None):
-        """keep_weight_grads: on the single-GPU bf16 FusedAdam path the 2-D weights are stepped inside their weight-gradient GEMMs and
+                 launch_list: Optional[bool] = None, keep_weight_grads: Optional[bool] = None, loss_stats: Optional[bool] = None):
+        """loss_stats: True / False sets model.cap_decoder.loss_stats (None leaves it): the caption loss then also leaves the
+        un-smoothed NLL and the token accuracy on the device at label_smoothing 0 (last_nll, last_token_acc); with label_smoothing > 0
+        they are always there.
+        keep_weight_grads: on the single-GPU bf16 FusedAdam path the 2-D weights are stepped inside their weight-gradient GEMMs and
         their gradients are NOT stored (model.grads_valid is False after a step; the reference leaves valid .grad after backward,
         train.py:125).  True stores them as well (for clipping, logging, hooks; costs the 4 B per parameter the fusion saved);
         None: the VCT_FUSE_ADAM_KEEP_GRAD environment switch (default off).
@@ -60,6 +63,12 @@ class CaptionTrainer:
         # grow-only buffers, so the views Python published for the LAST shape it ran have another shape's dimensions
         self._attn = {}
         self._gen = None                  # the buffer generation (engine.StepContext) the recordings were made at
+        # the caption loss's by-products (label smoothing / loss_stats): fp32 [2] in the decoder engine's buffer set, per input shape
+        if loss_stats is not None:
+            model.cap_decoder.loss_stats = bool(loss_stats)
+        self._stats = None                # the (NLL, token accuracy) buffer the LAST step wrote, or None
+        self._stats_of = {}               # per input shape: the buffer that shape's recording writes
+        self._stats_mode = self._loss_stats_mode()
         if single and model.flat_grads.is_cuda:
             # this trainer (zero_grad implicit, no exchange, no in-place averaging) is the only writer of the gradient buffer
             model.cap_decoder._engine().exclusive_grads = True
@@ -80,6 +89,35 @@ class CaptionTrainer:
         self.clipper = None
         self._clip_mode = None
         self._sync_clip()
+
+    # ---- NLL and token accuracy beside a smoothed loss --------------------------------------------------------------------------------
+    def _loss_stats_mode(self):
+        dec = self.model.cap_decoder
+        return (float(dec.cfg.get("label_smoothing", 0.0)), bool(dec.loss_stats))
+
+    def _sync_loss_stats(self):
+        """Recordings bake which loss entry point a step launches (and its smoothing, a launch scalar): drop them when
+        cap_decoder.loss_stats or the smoothing was changed since.  Host-only."""
+        mode = self._loss_stats_mode()
+        if mode != self._stats_mode:
+            self._stats_mode = mode
+            self.drop_recordings()
+
+    def _published_stats(self):
+        return self.model.cap_decoder._engine().last_loss_stats
+
+    @property
+    def last_nll(self):
+        """0-dim device fp32: the un-smoothed negative log-likelihood per non-pad token of the last caption step (fairseq's
+        nll_loss), a view of the engine's buffer that the next step rewrites; no synchronisation.  None unless that step ran the
+        smoothed entry point: label_smoothing > 0, or loss_stats."""
+        return None if self._stats is None else self._stats[0]
+
+    @property
+    def last_token_acc(self):
+        """0-dim device fp32: the share of non-pad tokens whose label held the row's largest logit (a tie counts) in the last caption
+        step.  None under last_nll's conditions."""
+        return None if self._stats is None else self._stats[1]
 
     # ---- gradient clipping -------------------------------------------------------------------------------------------------------------
     def _sync_clip(self):
@@ -152,6 +190,7 @@ class CaptionTrainer:
         if m.training and m.video_encoder.cfg["dropout"] > 0:
             ops.advance_seed(m._seed)
         ops.tap("step", 1)
+        self._stats = self._published_stats() if self.task == "cross" else None
         return out
 
     def _check_scst(self, num_samples, baseline):
@@ -188,6 +227,7 @@ class CaptionTrainer:
         launch (the reward kernel takes the start column + 64 tokens)."""
         self._check_scst(num_samples, baseline)
         self._sync_clip()
+        self._stats = None                      # the policy-gradient loss (ops.wce_loss) ignores label smoothing and leaves no NLL / accuracy
         if getattr(reward_fn, "on_device", False):
             return self._scst_step_device(feats, mask, reward_fn, vids, int(num_samples), baseline, max_len, temperature, top_k, top_p,
                                           seed)
@@ -359,6 +399,7 @@ class CaptionTrainer:
         self._lists.clear()
         self._graphs.clear()
         self._attn.clear()
+        self._stats_of.clear()
 
     def _static_inputs(self, key, feats, mask, ids):
         s = self._static.get(key)
@@ -424,6 +465,7 @@ class CaptionTrainer:
         if self._fused:
             self.opt.sync_hyper()
         self._sync_clip()
+        self._sync_loss_stats()
         if self.fuse_adam:
             # the embedding's live-row table exists and is true before the step is enqueued, recorded or replayed (host-only check
             # unless an optimizer state was loaded or a dense pass ran over the table since the last step)
@@ -432,7 +474,9 @@ class CaptionTrainer:
             self._check_task(task)
             return self._step_task(feats, mask, ids, text_feats)
         if not (self.use_graph or self.use_list):
-            return self._step_kernels(feats, mask, ids)
+            loss = self._step_kernels(feats, mask, ids)
+            self._stats = self._published_stats()
+            return loss
         self._check_generation()
         key = self._input_key(feats, mask, ids)
         static = self._static_inputs(key, feats, mask, ids)
@@ -442,18 +486,21 @@ class CaptionTrainer:
             # first step of this shape: run it eagerly on the static copies (allocates every buffer), then record the same
             # schedule; later calls replay the recording
             eager_loss = self._step_kernels(*static).clone()
+            self._stats = self._published_stats()
             self._check_generation()                # the eager step allocated: older recordings are stale, this one is not made yet
             hit = record(static)
             if hit is not None:
                 cache[key] = hit
                 if self.model.cap_decoder.custom_decoder_type is not None:
                     self._attn[key] = self.model.cap_decoder.attn_weights
+                self._stats_of[key] = self._stats
             return eager_loss
         recording, loss = hit
         self._fresh_shadow()
         recording.replay()
         if key in self._attn:                       # a replay runs no Python forward: publish THIS shape's views of the maps it wrote
             self.model.cap_decoder.attn_weights = self._attn[key]
+        self._stats = self._stats_of.get(key)
         self.model._ps.shadow_replayed()            # the replayed optimizer rewrote the shadow
         return loss
 
