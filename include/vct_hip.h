@@ -546,14 +546,24 @@ int vct_embed_live_rebuild(int32_t V, int32_t d, const float* grad_rows, const f
                            uint8_t* live, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Symmetric cross-entropy loss + gradient w.r.t. logits, one workgroup per row, row held in registers
- * (one HBM read + one exp + one HBM write per logit).  Limits: ldl, ld_dl multiples of 8 (bf16) / 4 (fp32),
- * >= V rounded up to that, and <= 65536 (bf16) / 32768 (fp32) columns.
+ * The caption losses over the vocabulary logits (csrc/vct_caption_loss.hip): vct_sce_loss, vct_sce_loss_ls, vct_wce_loss -- one
+ * kernel family.  Each returns the loss and, unless dlogits is NULL, its gradient w.r.t. the logits; one workgroup per row, the row
+ * held in registers (one HBM read + one exp + one HBM write per logit).  What the three share:
+ *   logits [N, ldl] (V valid columns); labels int64: row n = (b = n / S, s = n % S) ->
+ *   labels[b*label_batch_stride + s]  (so tgt[:, 1:] needs no copy); row n is valid when its label y != pad_id;
+ *   count = number of valid rows;  lse, p over the V columns.
+ *   loss_out fp32 [1]; dlogits (may alias logits; columns V..ld_dl-1 are written as 0) or NULL = forward only; ld_dl is ignored
+ *   when dlogits is NULL.
+ *   Limits: ldl, ld_dl multiples of 8 (bf16) / 4 (fp32), >= V rounded up to that, and <= 65536 (bf16) / 32768 (fp32) columns;
+ *   logits and dlogits 16-byte aligned.  VCT_E_ARG: bad dtype / NULL logits, labels, loss_out or row_ws; VCT_E_SHAPE: N, S, V <= 0,
+ *   N not a multiple of S, a row wider than the limit; VCT_E_ALIGN: ldl / ld_dl / a base address off the rules above.
+ *   A label outside [0, V) on a valid row is computed against column 0 (no stray access) and turns the loss into NaN.
+ *   count == 0: the loss is 0 / 0 = NaN, every gradient row is zero.
+ *   Two calls are bitwise equal (fixed-order single-workgroup count and finalise, no float atomics).
+ *
+ * vct_sce_loss: symmetric cross-entropy,  loss = alpha * sum CE_n / count + (1 - alpha) * mean over all N rows of RCE_n.
  * replaces: SCELoss.forward (loss.py:78-92) / nn.CrossEntropyLoss(ignore_index) when alpha == 1
  * (CapDecoder.py:28-32,56-59) and their autograd backward.
- *   logits [N, ldl] (V valid columns); labels int64: row n = (b = n / S, s = n % S) ->
- *   labels[b*label_batch_stride + s]  (so tgt[:, 1:] needs no copy).
- *   loss_out fp32 [1]; dlogits (may alias logits; columns V..ldl-1 are written as 0) or NULL.
  *   row_ws fp32 [2*N + 2] scratch.
  * --------------------------------------------------------------------------------------------- */
 int vct_sce_loss(int dtype, int N, int S, int V, const void* logits, int64_t ldl, const int64_t* labels,
@@ -561,43 +571,37 @@ int vct_sce_loss(int dtype, int N, int S, int V, const void* logits, int64_t ldl
                  int64_t ld_dl, float* row_ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * vct_sce_loss with label smoothing on its CE term, plus the un-smoothed NLL and the token accuracy (csrc/vct_sce_ls.hip).
+ * vct_sce_loss with label smoothing on its CE term, plus the un-smoothed NLL and the token accuracy.
  * replaces: nn.CrossEntropyLoss(ignore_index, label_smoothing) at alpha == 1; the reference's SCELoss has no smoothing -- with
  * alpha < 1 the CE term is smoothed and the RCE term is vct_sce_loss's, unchanged.
- *   eps = smoothing in [0, 1);  row n valid when its label y != pad_id;  count = number of valid rows;  lse, p over the V columns
+ *   eps = smoothing in [0, 1)
  *   nll_n = lse - x[y];  smooth_n = lse - (1/V) sum_{j<V} x[j];  ce_n = (1 - eps) nll_n + eps smooth_n  (0 on pad rows)
  *   loss_out[0] = alpha * sum ce_n / count + (1 - alpha) * L_rce               (L_rce: vct_sce_loss's, mean over all N rows)
  *   dlogits[n, j] = (alpha / count) (p_j - (1 - eps) [j == y] - eps / V) [valid] + vct_sce_loss's RCE part; columns V..ld_dl-1 = 0
  *   stats_out[0] = sum over valid n of nll_n / count;  stats_out[1] = #{valid n: x[y] == max_j x[j]} / count (a tie with the
  *   maximum counts as a hit; a label outside the vocabulary as a miss)                              (fp32 [2] or NULL)
  * smoothing == 0 gives vct_sce_loss's loss_out and dlogits bit for bit.  smoothing outside [0, 1) or NaN: VCT_E_ARG, nothing
- * launched.  Limits, alignment, aliasing (dlogits may be logits; NULL = forward only), the out-of-vocabulary label (column 0; NaN
- * loss and NaN stats_out[0]), count == 0 and the other return codes are vct_sce_loss's.  row_ws fp32 [4*N + 2] scratch.  Two calls
- * are bitwise equal (fixed-order single-workgroup count and finalise, no float atomics).
+ * launched.  The out-of-vocabulary label also makes stats_out[0] NaN.  row_ws fp32 [4*N + 2] scratch.
  * --------------------------------------------------------------------------------------------- */
 int vct_sce_loss_ls(int dtype, int N, int S, int V, const void* logits, int64_t ldl, const int64_t* labels,
                     int64_t label_batch_stride, int64_t pad_id, float alpha, float smoothing, float* loss_out,
                     float* stats_out, void* dlogits, int64_t ld_dl, float* row_ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Sequence-weighted cross-entropy for self-critical sequence training (csrc/vct_wce_loss.hip): vct_sce_loss at alpha = 1 with
+ * Sequence-weighted cross-entropy for self-critical sequence training: vct_sce_loss at alpha = 1 with
  * one weight (the advantage) per sequence.  The reference has no policy-gradient stage; the semantics are DESIGN.md's.
- *   row n belongs to sequence b = n / S, label = labels[b*label_batch_stride + n % S], valid when label != pad_id;
- *   count = number of valid rows;  logp_n = x[y] - max - log(sum exp(x - max)) in fp32
+ *   row n belongs to sequence b = n / S;  logp_n = x[y] - max - log(sum exp(x - max)) in fp32
  *   loss_out[0] = -(sum over valid n of seq_w[b] * logp_n) / count
  *   tok_logp[n] = logp_n on valid rows, exactly 0 on pad rows                                  (fp32 [N] or NULL)
- *   dlogits[n, j] = (seq_w[b] / count) * (p_j - [j == y]) on valid rows, exact zeros on pad rows and in columns V..ld_dl-1
- *   (may alias logits; NULL = forward only).
+ *   dlogits[n, j] = (seq_w[b] / count) * (p_j - [j == y]) on valid rows, exact zeros on pad rows and in columns V..ld_dl-1.
  * seq_w: DEVICE fp32 [N / S], read by the kernel (a recording stays valid across steps), or NULL = all ones.  With NULL or with
- * all 1.0f, loss and dlogits are bitwise those of vct_sce_loss(alpha = 1).  Limits, alignment, the out-of-vocabulary label
- * (column 0, NaN loss), count == 0, row_ws fp32 [2*N + 2] and the return codes are vct_sce_loss's.  Two calls are bitwise equal
- * (fixed-order single-workgroup count and finalise, no float atomics).
+ * all 1.0f, loss and dlogits are bitwise those of vct_sce_loss(alpha = 1).  row_ws fp32 [2*N + 2] scratch.
  * --------------------------------------------------------------------------------------------- */
 int vct_wce_loss(int dtype, int N, int S, int V, const void* logits, int64_t ldl, const int64_t* labels,
                  int64_t label_batch_stride, int64_t pad_id, const float* seq_w, float* loss_out, float* tok_logp,
                  void* dlogits, int64_t ld_dl, float* row_ws, void* stream);
 
-/* out[g*R + r, :] = sum over n < G of in[(g*G + n)*R + r, :] for g < B, r < R: `in` [B*G*R, d] and `out` [B*R, d] contiguous rows
+/* (csrc/vct_caption_loss.hip)  out[g*R + r, :] = sum over n < G of in[(g*G + n)*R + r, :] for g < B, r < R: `in` [B*G*R, d] and `out` [B*R, d] contiguous rows
  * of the compute dtype, 16-byte aligned, d a multiple of 8 (bf16) / 4 (fp32).  fp32 accumulation in ascending n, one rounding into
  * the compute dtype; G = 1 is a bitwise copy.  Folds d(memory) of G sampled captions per video back onto the video's memory rows.
  * VCT_E_ARG: bad dtype / NULL; VCT_E_SHAPE: B, G, R, d <= 0 or d not a multiple of the vector; VCT_E_ALIGN: misaligned base. */

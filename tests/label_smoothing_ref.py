@@ -1,5 +1,5 @@
 """fp64 reference, derived per-element bounds, checkers and a fault-injecting float32 emulation of the label-smoothed symmetric
-cross-entropy (include/vct_hip.h: vct_sce_loss_ls, csrc/vct_sce_ls.hip).  Built on tests/row_ref.py's sce() -- the un-smoothed
+cross-entropy (include/vct_hip.h: vct_sce_loss_ls, csrc/vct_caption_loss.hip).  Built on tests/row_ref.py's sce() -- the un-smoothed
 operation with its bounds -- which this file imports and does not change.  Shared by tests/test_label_smoothing_cpu.py (which checks
 THIS file against torch.nn.functional.cross_entropy(label_smoothing=) and autograd, and shows that every checker rejects the fault
 meant for it) and tests/test_label_smoothing_kernels_gpu.py.  Nothing here reads the library.

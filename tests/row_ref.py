@@ -1,6 +1,6 @@
 """fp64 references, per-element bounds, checkers, shapes and a fault-injecting float32 emulation of the memory-bound row kernels:
 residual + LayerNorm forward / backward and its two-norm forms (csrc/vct_norm.hip), the dgamma / dbeta finalize, the symmetric
-cross-entropy loss (vct_sce_loss), the token embedding forward / backward (csrc/vct_elem.hip) and the flat Adam step
+cross-entropy loss (vct_sce_loss, csrc/vct_caption_loss.hip), the token embedding forward / backward (csrc/vct_elem.hip) and the flat Adam step
 (csrc/vct_optim.hip, vct_adam_core.h).  Shared by tests/test_row_ref_cpu.py (which checks THIS file against torch.nn.functional,
 autograd, torch.optim and oracle/vct_oracle.py, and shows that every checker rejects the seeded faults) and
 tests/test_row_kernels_gpu.py.  Plain torch in float64 on whatever device the operands live on; nothing here reads the library.

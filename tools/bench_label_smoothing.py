@@ -5,7 +5,8 @@ measurements between stream events, the cases alternating inside a round, all in
   {"bench": "label_smoothing_loss"}: us per loss call (count + row kernel + finalise) on 4864 rows x 30522 logits, bf16, in place, of
     sce        ops.sce_loss (vct_sce_loss), the shipped path;
     ls_eps0    ops.sce_loss_ls at smoothing 0 with the statistics;
-    ls_eps01   ops.sce_loss_ls at smoothing 0.1 with the statistics.
+    ls_eps01   ops.sce_loss_ls at smoothing 0.1 with the statistics;
+    wce        ops.wce_loss (vct_wce_loss) with a random device seq_w and tok_logp.
     Each case owns its logits buffer, refilled with the same random logits before every measurement (a call overwrites it with the
     gradient).
   {"bench": "label_smoothing_step"}: ms per training step on the recorded launch list, dropout on, --steps steps per measurement, of
@@ -56,10 +57,12 @@ def bench_loss(batch, calls, rounds, alpha):
     ids[::3, S - 4:] = 0                                            # pad tails
     loss, stats = torch.zeros(1, device=dev), torch.zeros(2, device=dev)
     ws = torch.zeros(4 * N + 2, device=dev)
-    bufs = {k: torch.empty_like(src) for k in ("sce", "ls_eps0", "ls_eps01")}
+    seq_w, tok_logp = torch.randn(batch, device=dev, generator=g), torch.zeros(N, device=dev)
+    bufs = {k: torch.empty_like(src) for k in ("sce", "ls_eps0", "ls_eps01", "wce")}
     fns = {"sce": lambda: ops.sce_loss(bufs["sce"], V, ids[:, 1:], S - 1, 0, alpha, loss, bufs["sce"], ws),
            "ls_eps0": lambda: ops.sce_loss_ls(bufs["ls_eps0"], V, ids[:, 1:], S - 1, 0, alpha, 0.0, loss, bufs["ls_eps0"], ws, stats=stats),
-           "ls_eps01": lambda: ops.sce_loss_ls(bufs["ls_eps01"], V, ids[:, 1:], S - 1, 0, alpha, 0.1, loss, bufs["ls_eps01"], ws, stats=stats)}
+           "ls_eps01": lambda: ops.sce_loss_ls(bufs["ls_eps01"], V, ids[:, 1:], S - 1, 0, alpha, 0.1, loss, bufs["ls_eps01"], ws, stats=stats),
+           "wce": lambda: ops.wce_loss(bufs["wce"], V, ids[:, 1:], S - 1, 0, seq_w, loss, bufs["wce"], ws, tok_logp=tok_logp)}
     for k, fn in fns.items():
         bufs[k].copy_(src)
         _events(fn, 3)

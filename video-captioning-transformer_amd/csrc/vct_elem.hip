@@ -1,7 +1,6 @@
 // HBM-bound pieces of the caption path on gfx950: encoder front end (mean token + temporal
-// encoding), token embedding gather / deterministic scatter-add, the symmetric-cross-entropy loss
-// with its logits gradient (row resident in LDS: one HBM read + one HBM write per logit), casts,
-// first-index arg-max, dropout seed advance.  All loads/stores are 16-byte vectors where the
+// encoding), token embedding gather / deterministic scatter-add, casts, first-index arg-max,
+// dropout seed advance (the caption losses: vct_caption_loss.hip).  All loads/stores are 16-byte vectors where the
 // layout allows; reductions use wave shuffles + a few LDS words.
 #include "vct_common.h"
 
@@ -327,149 +326,6 @@ __global__ __launch_bounds__(1024) void embed_bwd_kernel(int N, int d, int V, co
 }
 
 // ---------------------------------------------------------------------------------------------
-// SCE loss + dlogits.  One 1024-thread workgroup per row; the row sits in LDS as fp32.
-// ---------------------------------------------------------------------------------------------
-__global__ void count_valid_kernel(int N, int S, const int64_t* __restrict__ labels, int64_t lbstride, int64_t pad_id,
-                                   float* __restrict__ out) {
-  __shared__ float red[16];
-  float c = 0.0f;
-  for (int n = threadIdx.x; n < N; n += blockDim.x) c += (labels[(size_t)(n / S) * lbstride + (n % S)] != pad_id) ? 1.0f : 0.0f;
-  c = block_sum<16>(c, red);
-  if (threadIdx.x == 0) out[0] = c;
-}
-
-constexpr float SCE_C = 9.210340371976184f;  // -log(1e-4): loss.py:86-88 off-target log(clamp(onehot))
-
-// One NT-thread workgroup per row; the row lives in REGISTERS (IT 16-byte vectors per thread, loaded
-// once from HBM), so every logit costs one HBM read, one exp and one HBM write (the gradient), and
-// LDS only carries the block reductions.  NT*IT vectors must cover the row: 512 x 8 for bf16 rows up to 4096 vectors (measured best; 256 x 16: few waves per
-// barrier, 16 loads in flight per thread, 3 rows per CU) or 1024 x 8 for very wide vocabularies.
-template <typename T, int IT, int NT>
-__global__ __launch_bounds__(NT, NT / 128) void sce_loss_kernel(int N, int S, int V, const T* __restrict__ logits, int64_t ldl,
-                                                        const int64_t* __restrict__ labels, int64_t lbstride,
-                                                        int64_t pad_id, float alpha, T* __restrict__ dlogits, int64_t ld_dl,
-                                                        float* __restrict__ row_ws) {
-  // one LDS array per block reduction: each costs ONE barrier (no guard barrier before reusing a shared scratch)
-  __shared__ float red_m[16], red_s[16], red_q[16], red_c[16];
-  constexpr int VEC = EV<T>::VEC, NW = NT / 64;
-  using P = PackT<T, VEC>;
-  const int n = blockIdx.x, tid = threadIdx.x, wv = tid >> 6, ln = tid & 63;
-  const T* x = logits + (size_t)n * ldl;
-  const int64_t y_in = labels[(size_t)(n / S) * lbstride + (n % S)];
-  const bool valid = (y_in != pad_id);
-  // a label outside the vocabulary (torch raises a device assert there) must not become a stray read / write: the row is
-  // computed against column 0 and, when it counts towards the loss, poisons it with NaN so the step fails loudly
-  const bool oob = (y_in < 0 || y_in >= V);
-  const int64_t y = oob ? 0 : y_in;
-  const float nvalid = row_ws[2 * N];
-  const float xy = to_f<T>(x[y]);
-  const int nv = (V + VEC - 1) / VEC;                 // vectors holding valid columns (ldl covers the rounded-up row)
-  // all IT loads are issued back to back, unconditionally (index clamped, out-of-row vectors masked after)
-  P pk[IT];
-#pragma unroll
-  for (int it = 0; it < IT; it++) pk[it] = *reinterpret_cast<const P*>(x + (size_t)min(it * NT + tid, nv - 1) * VEC);
-  float e[IT][VEC];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int it = 0; it < IT; it++) {
-    const int vi = it * NT + tid;
-#pragma unroll
-    for (int j = 0; j < VEC; j++) e[it][j] = to_f<T>(pk[it].v[j]);
-    if (vi >= nv - 1) {                                // only the last vector of the row (and beyond) needs masking
-#pragma unroll
-      for (int j = 0; j < VEC; j++)
-        if (vi >= nv || vi * VEC + j >= V) e[it][j] = -INFINITY;
-    }
-#pragma unroll
-    for (int j = 0; j < VEC; j++) mx = fmaxf(mx, e[it][j]);
-  }
-  mx = wave_max(mx);
-  if (ln == 0) red_m[wv] = mx;
-  __syncthreads();
-  mx = red_m[0];
-#pragma unroll
-  for (int i = 1; i < NW; i++) mx = fmaxf(mx, red_m[i]);
-  float se = 0.0f;
-#pragma unroll
-  for (int it = 0; it < IT; it++)
-#pragma unroll
-    for (int j = 0; j < VEC; j++) { e[it][j] = __expf(e[it][j] - mx); se += e[it][j]; }   // padding: exp(-inf) = 0
-  se = wave_sum(se);
-  if (ln == 0) red_s[wv] = se;
-  __syncthreads();
-  se = 0.0f;
-#pragma unroll
-  for (int i = 0; i < NW; i++) se += red_s[i];
-  const float inv = 1.0f / se;
-  const float beta = 1.0f - alpha;
-  const float py = __expf(xy - mx) * inv;
-  // over ALL columns: Qa = sum_{p_j >= 1e-7} p_j, ca = #{p_j < 1e-7} (padding has p = 0 and is counted: fixed below);
-  // the label column is then taken out analytically -- no per-element (j != y) tests
-  float q = 0.0f, cnt = 0.0f;
-  if (alpha != 1.0f) {
-#pragma unroll
-    for (int it = 0; it < IT; it++)
-#pragma unroll
-      for (int j = 0; j < VEC; j++) {
-        const float pj = e[it][j] * inv;
-        const bool big = pj >= 1e-7f;
-        q += big ? pj : 0.0f;
-        cnt += big ? 0.0f : 1.0f;
-      }
-    q = wave_sum(q);
-    cnt = wave_sum(cnt);
-    if (ln == 0) { red_q[wv] = q; red_c[wv] = cnt; }
-    __syncthreads();
-    q = 0.0f; cnt = 0.0f;
-#pragma unroll
-    for (int i = 0; i < NW; i++) { q += red_q[i]; cnt += red_c[i]; }
-    cnt -= (float)(IT * NT * VEC - V);                 // masked / padding slots were counted as "small"
-    if (py >= 1e-7f) q -= py; else cnt -= 1.0f;        // remove the label column
-  }
-  if (tid == 0) {
-    row_ws[n] = valid ? (oob ? __builtin_nanf("") : (mx + __logf(se)) - xy) : 0.0f;
-    row_ws[N + n] = SCE_C * (q + 1e-7f * cnt);
-  }
-  if (dlogits == nullptr) return;
-  // gradient for j != y:  p_j * (a + bn*(G_j - c*Q)),  G_j = c*[p_j >= 1e-7]; padding has p = 0 -> 0
-  const float a = valid ? alpha / nvalid : 0.0f;
-  const float bn = (alpha != 1.0f) ? beta / (float)N : 0.0f;
-  const float k_small = a - bn * SCE_C * q;            // multiplier when p_j <  1e-7
-  const float k_big = k_small + bn * SCE_C;            // multiplier when p_j >= 1e-7
-  T* dx = dlogits + (size_t)n * ld_dl;
-  const int nvo = (int)(ld_dl / VEC);
-#pragma unroll
-  for (int it = 0; it < IT; it++) {
-    const int vi = it * NT + tid;
-    if (vi < nvo) {
-      P o;
-#pragma unroll
-      for (int j = 0; j < VEC; j++) {
-        const float pj = e[it][j] * inv;
-        o.v[j] = from_f<T>(pj * (pj >= 1e-7f ? k_big : k_small));
-      }
-      *reinterpret_cast<P*>(dx + vi * VEC) = o;
-    }
-  }
-  // the label column: a*(p_y - 1) + bn*p_y*(0 - c*Q)   (written after the row's vector stores)
-  __syncthreads();
-  if (tid == 0) dx[y] = from_f<T>(a * (py - 1.0f) - bn * py * SCE_C * q);
-}
-
-__global__ void sce_finalize_kernel(int N, float alpha, const float* __restrict__ row_ws, float* __restrict__ loss) {
-  __shared__ float red[16];
-  float ce = 0.0f, rce = 0.0f;
-  for (int n = threadIdx.x; n < N; n += blockDim.x) { ce += row_ws[n]; rce += row_ws[N + n]; }
-  ce = block_sum<16>(ce, red);
-  rce = block_sum<16>(rce, red);
-  if (threadIdx.x == 0) {
-    const float nvalid = row_ws[2 * N];
-    const float l_ce = ce / nvalid;
-    loss[0] = (alpha == 1.0f) ? l_ce : alpha * l_ce + (1.0f - alpha) * (rce / (float)N);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
 // a same-type cast is a copy of the bits (bf16 -> fp32 -> bf16 through the hardware conversion would quiet a signalling NaN)
 template <typename TS, typename TD> __device__ __forceinline__ TD cast_one(TS v) {
   if constexpr (std::is_same<TS, TD>::value) return v;
@@ -708,34 +564,6 @@ extern "C" int vct_embed_bwd_live(int dtype, int B, int S, int d, int V, const i
     vct::launch((embed_bwd_kernel<float>), grid, dim3(1024), heavy_lds, st, N, d, V, flat, (int32_t)pad_id, (const float*)dx, dtable,
                 first_pos, cnt, seed, site, p_drop);
   }
-  VCT_CHECK_LAUNCH();
-  return VCT_OK;
-}
-
-extern "C" int vct_sce_loss(int dtype, int N, int S, int V, const void* logits, int64_t ldl, const int64_t* labels,
-                            int64_t label_batch_stride, int64_t pad_id, float alpha, float* loss_out, void* dlogits,
-                            int64_t ld_dl, float* row_ws, void* stream) {
-  if (!dt_ok(dtype) || !logits || !labels || !loss_out || !row_ws) return VCT_E_ARG;
-  if (N <= 0 || S <= 0 || V <= 0 || N % S) return VCT_E_SHAPE;
-  const int vec = vec_of(dtype);
-  const int64_t vround = ((int64_t)V + vec - 1) / vec * vec;
-  if (ldl < vround || ldl % vec || ((uintptr_t)logits & 15)) return VCT_E_ALIGN;       // rows are read as 16-byte vectors
-  if (dlogits && (ld_dl < vround || ld_dl % vec || ((uintptr_t)dlogits & 15))) return VCT_E_ALIGN;
-  if (ld_dl > (int64_t)8 * 1024 * vec || vround > (int64_t)8 * 1024 * vec) return VCT_E_SHAPE;   // row must fit the register tile
-  hipStream_t st = (hipStream_t)stream;
-  vct::launch(count_valid_kernel, dim3(1), dim3(1024), 0, st, N, S, labels, label_batch_stride, pad_id, row_ws + 2 * (size_t)N);
-  VCT_CHECK_LAUNCH();
-  const int64_t width = dlogits ? (ld_dl > vround ? ld_dl : vround) : vround;
-  const bool small = width <= (int64_t)4 * 1024 * vec;
-#define VCT_SCE(T_, IT_, NT_) vct::launch((sce_loss_kernel<T_, IT_, NT_>), dim3(N), dim3(NT_), 0, st, N, S, V, (const T_*)logits, ldl, \
-                                                 labels, label_batch_stride, pad_id, alpha, (T_*)dlogits, ld_dl, row_ws)
-  // bf16, rows up to 4096 vectors: 512 threads x 8 vectors (4 workgroups per CU) -- measured in the step at V = 30522: 114 us against
-  // 136 us for 1024 x 4 and 126 us for 256 x 16 (5.2 TB/s of HBM traffic)
-  if (dtype == VCT_BF16) { if (small) VCT_SCE(bf16_t, 8, 512); else VCT_SCE(bf16_t, 8, 1024); }
-  else { if (small) VCT_SCE(float, 4, 1024); else VCT_SCE(float, 8, 1024); }
-#undef VCT_SCE
-  VCT_CHECK_LAUNCH();
-  vct::launch(sce_finalize_kernel, dim3(1), dim3(1024), 0, st, N, alpha, row_ws, loss_out);
   VCT_CHECK_LAUNCH();
   return VCT_OK;
 }
