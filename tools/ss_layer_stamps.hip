@@ -74,6 +74,7 @@ static void run(int cross, int B, int L, int Lm, float p_drop) {
 
 int main() {
   run(0, 256, 13, 0, 0.3f);
+  run(0, 256, 13, 0, 0.0f);
   run(1, 256, 19, 13, 0.3f);
   run(1, 256, 19, 13, 0.0f);
   return 0;

@@ -37,10 +37,23 @@
 //                                                          behind a barrier) and the chunk loop
 //     cross q (R1C), k | v (R0), o2 (R1A)  cross out_proj  LN2 writes a2 -> R1C behind its first barrier (AP_LATE), x2 -> R0 behind both
 //     a2 (R1C), x2 (R0)                    linear1(0)      chunk 0's activation goes to R1B; R1C is chunk 1's, behind the first chunk barrier
-//     h chunk j (R1B / R0 | R1C)           linear2 slice j the buffer is rewritten by chunk j + 2, two barriers later
+//     h chunk j (R1B / R0 | R1C)           linear2 slice j the buffer is rewritten by chunk j + 2: behind two barriers, or (the last chunk,
+//                                                          below) behind one
 //     y (R0) of a layer that has a successor in the launch: that layer's first q | k | v block (x is read-only up to the attention)
 // f (R1A) and the final norm's output (R1C) are overwritten by the next q | k | v block's epilogue with no barrier in between, and the
 // last layer of a launch has no product behind it: those copies stay synchronous.  (tests/test_layer_ss_overlap_gpu.py)
+//
+// The same callbacks carry vector ALU work that would otherwise run bare, with the stream stalled (tests/test_layer_ss_hidden_epilogues_gpu.py):
+//     GELU / dropout of the LAST chunk nj - 1 -> HP[(nj - 1) & 1]      linear2 slice nj - 2 (ff >= 1024), one 16 x 16 tile per K step.  The
+//         buffer's last readers are linear2(nj - 3) and the copy that slice carried (nj = 2: R1C's a2 copy under linear1(0) of a
+//         decoder layer); all of them are complete at the chunk barrier every wave passes before it enters slice nj - 2.  Every chunk's
+//         pre-activation leaves the accumulators directly behind its linear1, so the tiles find it in hpk.  ff = 512 has no earlier
+//         slice: its one epilogue runs bare.
+//     keep bits of the dropout in front of LN1 / LN2 / the closing norm        out_proj / cross out_proj / the last linear2 slice
+//         (ln_keep_slice: pure register work, the counter hash of (seed, site, element index); epi_ln turns a bit into 0 or 1 / (1 - p))
+// Left out, with its numbers: the attention masks as bits (hashed under the third q | k | v block and the cross k | v blocks) need one
+// more live register through the attention and cost 2-3 spilled VGPRs (scratch 12-16 B/lane) in the two-row-tile kernels, which sit at
+// 253 / 255 registers without it.  (profiles/ss_fwd_hidden_epilogues_ab.txt)
 #include "vct_layer_ss_core.h"
 
 namespace vct {
@@ -100,7 +113,7 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
     ss_barrier();
     f32x4 au[MT][SS_TPW];
     acc_zero<MT>(au);
-    wave_gemm<MT>(au, R1A + li * SS_PSTR + lg * 8, SS_PSTR, 0, 8, ws, b0, b1);
+    wave_gemm<MT, true>(au, R1A + li * SS_PSTR + lg * 8, SS_PSTR, 0, 8, ws, b0, b1);
     const float invT = 1.0f / (float)T;
 #pragma unroll
     for (int t = 0; t < SS_TPW; t++) {
@@ -205,7 +218,7 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
           panel_to_global_slice<SS_D, decltype(K)::value, 0, IT1, IT1>(R0, SS_PSTR, L, gy, SS_D, grow0, 0, tid);
         });
       } else {
-        wave_gemm<MT>(acc, R0 + aoff, SS_PSTR, 0, 8, ws, b0, b1);
+        wave_gemm<MT, true>(acc, R0 + aoff, SS_PSTR, 0, 8, ws, b0, b1);
       }
       epi_store<MT>(acc, bv, R1A, SS_QSTR, nb * 512 + wave * SS_CPW, li, lg);
     }
@@ -230,15 +243,17 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
       load_bias4(bv, w.b_o, wave * SS_CPW, lg);
       acc_zero<MT>(acc);
       bf16_t* const gqkv = w.qkv; bf16_t* const go = w.o;
+      const Dropout dr = make_dropout(p.seed, w.site_n1, p.p_drop);
+      uint32_t keep = ln_keep_init(dr);                    // LN1's dropout mask, as bits: hashed between the K steps
       wave_gemm8_cb<MT>(acc, R0 + aoff, SS_PSTR, ws, b0, b1, [&](auto K) {
         constexpr int k = decltype(K)::value;
         panel_to_global_slice<3 * SS_D, k, 0, IT3, IT3 + IT1>(R1A, SS_QSTR, L, gqkv, 3 * SS_D, grow0, 0, tid);
         panel_to_global_slice<SS_D, k, IT3, IT1, IT3 + IT1>(R0, SS_PSTR, L, go, SS_D, grow0, 0, tid);
+        ln_keep_slice<MT, k>(keep, dr, grow0, wave, tid);
       });
       SS_STAMP(8);
-      const Dropout dr = make_dropout(p.seed, w.site_n1, p.p_drop);
       // AP = R1A is still q of the copy other waves carry: its stores wait for the epilogue's first barrier (AP_LATE)
-      epi_ln<MT, true>(acc, bv, res, nrm(w.n1), SsNorm{}, false, dr, grow0, L, R1A, R1B, nullptr, red, wave, li, lg);
+      epi_ln<MT, true>(acc, bv, res, nrm(w.n1), SsNorm{}, false, dr.scale, keep, grow0, L, R1A, R1B, nullptr, red, wave, li, lg);
       SS_STAMP(9);
     }
     ss_barrier();
@@ -262,7 +277,7 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
         f32x4 acm[1][SS_TPW];
         load_bias4(bv, w.b_ckv, nb * 512 + wave * SS_CPW, lg);
         acc_zero<1>(acm);
-        wave_gemm<1>(acm, RMp + aoff, SS_PSTR, 0, 8, ws, b0, b1);
+        wave_gemm<1, true>(acm, RMp + aoff, SS_PSTR, 0, 8, ws, b0, b1);
         epi_store<1>(acm, bv, R0, SS_KVSTR, nb * 512 + wave * SS_CPW, li, lg);
       }
       SS_STAMP(12);
@@ -285,16 +300,18 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
         load_bias4(bv, w.b_co, wave * SS_CPW, lg);
         acc_zero<MT>(acc);
         bf16_t* const gcq = w.cq; bf16_t* const gckv = w.ckv; bf16_t* const gco = w.co;
-        wave_gemm8_cb<MT>(acc, R1A + aoff, SS_PSTR, ws, b0, b1, [&](auto K) {     // carries the copies of the cross q, k | v and o
+        const Dropout dr = make_dropout(p.seed, w.site_n2, p.p_drop);
+        uint32_t keep = ln_keep_init(dr);
+        wave_gemm8_cb<MT>(acc, R1A + aoff, SS_PSTR, ws, b0, b1, [&](auto K) {     // carries the copies of the cross q, k | v and o, and LN2's mask bits
           constexpr int k = decltype(K)::value, tot = 2 * IT1 + ITKV;
           panel_to_global_slice<SS_D, k, 0, IT1, tot>(R1C, SS_PSTR, L, gcq, SS_D, grow0, 0, tid);
           panel_to_global_slice<2 * SS_D, k, IT1, ITKV, tot>(R0, SS_KVSTR, Lm, gckv, 2 * SS_D, (long)b * Lm, 0, tid);
           panel_to_global_slice<SS_D, k, IT1 + ITKV, IT1, tot>(R1A, SS_PSTR, L, gco, SS_D, grow0, 0, tid);
+          ln_keep_slice<MT, k>(keep, dr, grow0, wave, tid);
         });
         SS_STAMP(16);
-        const Dropout dr = make_dropout(p.seed, w.site_n2, p.p_drop);
         // AP = R1C is still the q of that copy: AP_LATE (YP = R0, the k | v panel, is written behind both barriers anyway)
-        epi_ln<MT, true>(acc, bv, res, nrm(w.n2), SsNorm{}, false, dr, grow0, L, R1C, R0, nullptr, red, wave, li, lg);
+        epi_ln<MT, true>(acc, bv, res, nrm(w.n2), SsNorm{}, false, dr.scale, keep, grow0, L, R1C, R0, nullptr, red, wave, li, lg);
         SS_STAMP(17);
       }
       ss_barrier();
@@ -305,7 +322,8 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
     //   linear1(0) | [linear1(j+1) GEMM with the GELU / dropout epilogue of chunk j between its K steps] | barrier | linear2(j) K slice | ...
     // The epilogue of a chunk is ~9 k cycles of vector ALU work that nothing else in the workgroup could overlap; issued between the
     // K steps of the NEXT chunk's linear1 it runs in the shadow of that product's weight stream.  The activation panel is double-
-    // buffered (one barrier per chunk); the pre-activation goes to HBM straight from the registers (8-byte stores).
+    // buffered (one barrier per chunk); the pre-activation goes to HBM straight from the registers (8-byte stores).  The LAST chunk's
+    // epilogue rides under the linear2 slice of the chunk in front of it (ff >= 1024; the file header has the slot argument).
     f32x4 facc[MT][SS_TPW];
     BV4 hpk[MT][SS_TPW];                                          // pre-activation of the chunk whose epilogue is pending, as stored (bf16)
     acc_zero<MT>(facc);
@@ -363,21 +381,37 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
     }
     ffn_pre(0);
     SS_STAMP(20);
-    for (int j = 0; j < nj; j++) {
-      if (j + 1 < nj) {
-        acc_zero<MT>(acc);
-        wave_gemm8_cb<MT>(acc, FIN + aoff, SS_PSTR, ws, b0, b1, [&](auto K) { ffn_tile(j, K); });
-      } else {
-        static_for<MT * SS_TPW>([&](auto K) { ffn_tile(j, K); });
-      }
+    // the closing norm's dropout mask: its keep bits are computed under the last linear2 slice
+    const Dropout dr3 = make_dropout(p.seed, w.site_n3, p.p_drop);
+    uint32_t keep3 = ln_keep_init(dr3);
+    // linear2's K slice that reads chunk j: carries the chunk's copy, and whatever `extra` adds per K step
+    auto lin2 = [&](const int j, auto&& extra) {
       SS_STAMP(21 + 4 * j);
       ss_barrier();
       bf16_t* HP = (j & 1) ? HP1 : HP0;
       SS_STAMP(22 + 4 * j);
-      wave_gemm8_cb<MT>(facc, HP + aoff, SS_PSTR, ws, b0, b1, [&](auto K) {      // the K slice that reads chunk j carries its copy
+      wave_gemm8_cb<MT>(facc, HP + aoff, SS_PSTR, ws, b0, b1, [&](auto K) {
         panel_to_global_slice<SS_D, decltype(K)::value, 0, IT1, IT1>(HP, SS_PSTR, L, gh, ff, grow0, j * 512, tid);
+        extra(K);
       });
-      if (j + 1 < nj) ffn_pre(j + 1);
+    };
+    for (int j = 0; j < nj; j++) {
+      if (j + 1 < nj) {
+        acc_zero<MT>(acc);
+        wave_gemm8_cb<MT>(acc, FIN + aoff, SS_PSTR, ws, b0, b1, [&](auto K) { ffn_tile(j, K); });
+        ffn_pre(j + 1);                                    // hpk is free: chunk j's tiles were issued under the product
+      } else if (nj == 1) {
+        static_for<MT * SS_TPW>([&](auto K) { ffn_tile(j, K); });      // one chunk: no earlier slice, its epilogue runs bare
+      }
+      // The LAST chunk has no linear1 behind it to carry its epilogue: the linear2 slice of the chunk in front of it issues the GELU /
+      // dropout tiles, one per K step, into the OTHER activation buffer.  That buffer's last readers (linear2(nj - 3) and the copy it
+      // carried) are complete at the chunk barrier every wave passes before it enters this slice.  The last slice hashes the closing
+      // norm's keep bits.  (ONE instance of the slice with wave-uniform branches in its callback: a second copy of the unrolled
+      // product costs ~100 spilled registers in the two-tile kernels.)
+      lin2(j, [&](auto K) {
+        if (j + 2 == nj) ffn_tile(j + 1, K);
+        if (j + 1 == nj) ln_keep_slice<MT, decltype(K)::value>(keep3, dr3, grow0, wave, tid);
+      });
       SS_STAMP(23 + 4 * j);
     }
     {                                                      // f = h W_2^T + b_2;  y = LN(x_in + drop(f)) [; y2 = LN_final(y)]
@@ -386,8 +420,7 @@ __global__ __launch_bounds__(SS_NT, SS_NW / 4) void layer_ss_fwd_kernel(const Ss
 #pragma unroll
         for (int t = 0; t < SS_TPW; t++) res[m][t] = *reinterpret_cast<const BV4*>(FIN + (m * 16 + li) * SS_PSTR + ecol + t * 16);
       ss_barrier();                                        // the last chunk's copy and linear2 reads are done: the activation buffers become y / y2
-      const Dropout dr = make_dropout(p.seed, w.site_n3, p.p_drop);
-      epi_ln<MT>(facc, bv, res, nrm(w.n3), nrm(kp->nf), fin, dr, grow0, L, FP, YP, Y2P, red, wave, li, lg);
+      epi_ln<MT>(facc, bv, res, nrm(w.n3), nrm(kp->nf), fin, dr3.scale, keep3, grow0, L, FP, YP, Y2P, red, wave, li, lg);
       SS_STAMP(40);
     }
     ss_barrier();

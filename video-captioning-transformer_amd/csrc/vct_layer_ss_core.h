@@ -121,12 +121,16 @@ __device__ __forceinline__ void gemm_step(f32x4 (&acc)[MT][SS_TPW], const bf16_t
 #pragma unroll
       for (int t = 0; t < SS_TPW; t++) acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[t][s], af[m][s], acc[m][t], 0, 0, 0);
 }
-template <int MT>
+// PIN: a scheduling fence behind the first re-fetch.  Without it the compiler may sink that re-fetch below the second K step (seen in the
+// forward kernel once its register budget is nearly used: all 16 loads issued together at the end of the iteration, so the next
+// iteration waits for a load issued a moment ago -- the q | k | v blocks went from 29 to 35 k cycles per decoder layer).
+template <int MT, bool PIN = false>
 __device__ __forceinline__ void wave_gemm(f32x4 (&acc)[MT][SS_TPW], const bf16_t* a, const int astr, const int kc0, const int nch, WStream& ws,
                                           bf16x8 (&b0)[SS_TPW][2], bf16x8 (&b1)[SS_TPW][2]) {
   for (int c = 0; c < nch; c += 2) {
     gemm_step<MT>(acc, a, astr, kc0 + c, b0);
     ws_fetch(ws, b0);
+    if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
     gemm_step<MT>(acc, a, astr, kc0 + c + 1, b1);
     ws_fetch(ws, b1);
   }
@@ -255,10 +259,34 @@ __device__ __forceinline__ void epi_store(const f32x4 (&acc)[MT][SS_TPW], const 
 // The norms come BY VALUE (has2: n2 is present): behind a pointer or a reference the structs live in private memory (scratch).
 // AP_LATE: the stores to AP wait (in registers) for the first barrier of the statistics -- for callers whose other waves may still be
 // reading AP's slot in its old role while this wave is already here (the deferred copies under the product in front of this epilogue).
+// The dropout mask comes as BITS (ln_keep_slice below): bit (m * SS_TPW + t) * 4 + r set = the element is kept (multiplier dscale).  The
+// hash behind a bit depends on (seed, site, element index) alone, so the product in front of the epilogue computes it between its K
+// steps, beside the weight stream, instead of the epilogue with the stream stalled.
+__device__ __forceinline__ uint32_t ln_keep_init(const Dropout& dr) { return dr.on ? 0u : ~0u; }     // dropout off: every bit set, scale 1
+template <int MT, int K>
+__device__ __forceinline__ void ln_keep_slice(uint32_t& keep, const Dropout& dr, const long grow0, const int wave, const int tid) {
+  static_assert(MT * SS_TPW * 4 <= 32, "one register of bits per lane");
+  if constexpr (K < MT * SS_TPW) {                       // K step K hashes tile (m, t) = (K / SS_TPW, K % SS_TPW): drop_mults<4>'s two pair hashes
+    if (dr.on) {
+      constexpr int m = K / SS_TPW, t = K % SS_TPW;
+      int tv = tid;                                      // opaque, as in panel_to_global_slice: the index is recomputed in its slice
+      asm volatile("" : "+v"(tv));
+      const int li = tv & 15, lg = (tv >> 4) & 3;
+      const uint32_t idx = (uint32_t)(grow0 + m * 16 + li) * (uint32_t)SS_D + (uint32_t)(wave * SS_CPW + lg * 4 + t * 16);   // even
+#pragma unroll
+      for (int k = 0; k < 2; k++) {
+        const uint32_t h = hash32((((idx >> 1) + (uint32_t)k) * 0x9E3779B1u) ^ dr.key);
+        keep |= ((h & 0xffffu) >= dr.thresh ? 1u : 0u) << (K * 4 + 2 * k);
+        keep |= ((h >> 16) >= dr.thresh ? 1u : 0u) << (K * 4 + 2 * k + 1);
+      }
+    }
+  }
+}
+
 template <int MT, bool AP_LATE = false>
 __device__ __forceinline__ void epi_ln(f32x4 (&acc)[MT][SS_TPW], const float4 (&bv)[SS_TPW], const BV4 (&res)[MT][SS_TPW], const SsNorm n, const SsNorm n2,
-                                       const bool has2, const Dropout& dr, const long grow0, const int L, bf16_t* AP, bf16_t* YP, bf16_t* Y2P, float* red,
-                                       const int wave, const int li_in, const int lg_in) {
+                                       const bool has2, const float dscale, const uint32_t keep, const long grow0, const int L, bf16_t* AP, bf16_t* YP,
+                                       bf16_t* Y2P, float* red, const int wave, const int li_in, const int lg_in) {
   // lane indices behind an opaque barrier: otherwise the address / counter arithmetic shared by the layer's three LayerNorm
   // epilogues is computed once and kept alive (spilled) from the first to the last of them
   int li = li_in, lg = lg_in;
@@ -273,12 +301,12 @@ __device__ __forceinline__ void epi_ln(f32x4 (&acc)[MT][SS_TPW], const float4 (&
 #pragma unroll
   for (int m = 0; m < MT; m++) {
     part[m] = 0.0f;
-    const uint32_t grow = (uint32_t)(grow0 + m * 16 + li);
 #pragma unroll
     for (int t = 0; t < SS_TPW; t++) {
       const float bb[4] = {bv[t].x, bv[t].y, bv[t].z, bv[t].w};
       float dm[4];
-      drop_mults<4>(dr, grow * (uint32_t)SS_D + (uint32_t)(colw + t * 16), dm);
+#pragma unroll
+      for (int r = 0; r < 4; r++) dm[r] = ((keep >> ((m * SS_TPW + t) * 4 + r)) & 1u) ? dscale : 0.0f;
       BV4 av;
 #pragma unroll
       for (int r = 0; r < 4; r++) {
