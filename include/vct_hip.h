@@ -1064,6 +1064,38 @@ typedef struct vct_logit_controls_desc {
 
 int vct_logit_controls(const vct_logit_controls_desc* d, void* stream);
 /* ---------------------------------------------------------------------------------------------
+ * Ensemble decoding (csrc/vct_ensemble.hip).  The reference decodes with one checkpoint; the semantics are the project's
+ * (decode.Ensemble): the next-token distributions of n models are averaged at every step, and the result is handed to the
+ * controls and selection kernels above as one fp32 row of log-probabilities (a row of log-probabilities is a valid logits row).
+ *
+ * vct_ensemble_combine: per row r and member m (fp32 throughout): z = float(x_m[r, v]), M_m = max_v z, S_m = sum_v exp(z - M_m),
+ * lp_m[v] = (z - M_m) - log S_m over the columns [0, V).  The weights w are READ FROM DEVICE MEMORY (fp32 [VCT_ENSEMBLE_MAX], the
+ * host normalises them: w_m >= 0, sum 1), so one captured graph serves every weighting.  A member with w_m == 0 (or a w_m that
+ * is not > 0) is skipped altogether -- not multiplied, so 0 * -inf cannot appear -- and none of its memory is read.
+ *   VCT_ENS_LOGP   out[r, v] = sum_m w_m lp_m[v], accumulated in member order (the geometric mean; the selection renormalises)
+ *   VCT_ENS_PROB   A = max over the members with w_m > 0 of lp_m[v];  out[r, v] = A + log sum_m w_m exp(lp_m[v] - A), -inf when
+ *                  A is -inf (the arithmetic mean of the probabilities)
+ * NaN in a member's row makes that row of out NaN and no other.  Columns >= V of x_m and of out are neither read nor written.
+ * One launch, one workgroup per row, three sweeps over each member's row (max, sum, combination: the second and third are served
+ * by the caches); 16-byte loads and stores where a tensor's base and row stride keep rows 16-byte aligned, element accesses
+ * otherwise and for the V % 8 tail.  Fixed-order reductions, no atomics, no workspace: a second call is bit-identical.
+ * VCT_E_ARG: NULL descriptor / x_m / w / out, bad dtype or mode; VCT_E_SHAPE: n outside 1 .. VCT_ENSEMBLE_MAX, rows < 1, V < 1,
+ * ld_m < V, ld_out < V.  All before any device use.
+ * --------------------------------------------------------------------------------------------- */
+#define VCT_ENSEMBLE_MAX 8
+enum { VCT_ENS_PROB = 0, VCT_ENS_LOGP = 1 };
+typedef struct vct_ensemble_desc {
+  int32_t n, mode, rows, V;                 /* members 1..8; columns [0, V) are read and written */
+  int32_t dtype[VCT_ENSEMBLE_MAX];          /* VCT_F32 | VCT_BF16 per member */
+  const void* x[VCT_ENSEMBLE_MAX];          /* member logits [rows, ld_m] */
+  int64_t ld[VCT_ENSEMBLE_MAX];
+  const float* w;                           /* DEVICE fp32 [VCT_ENSEMBLE_MAX]: w_m >= 0, sum 1 */
+  float* out;                               /* fp32 [rows, ld_out] */
+  int64_t ld_out;
+} vct_ensemble_desc;
+
+int vct_ensemble_combine(const vct_ensemble_desc* d, void* stream);
+/* ---------------------------------------------------------------------------------------------
  * One stage of the greedy-decode step at SMALL batch (B <= 4): out[b, n] = epilogue(W[n, :] . prologue(...)[b, :]), a weight-
  * streaming matrix-vector kernel whose prologue builds the input vector and whose epilogue finishes the stage, so that the
  * embedding / LayerNorm / attention launches of the per-token step vanish into their consumers (csrc/vct_decode.hip):

@@ -239,6 +239,17 @@ class LogitControlsDesc(C.Structure):
                 ("ids_stride", i64), ("ended", vp), ("parents", vp), ("parents_stride", i64), ("K", i32), ("reserved", i32), ("ctl", vp)]
 
 
+ENSEMBLE_MAX = 8
+ENS_MODE = {"prob": 0, "logp": 1}
+
+
+class EnsembleDesc(C.Structure):
+    """include/vct_hip.h, vct_ensemble_desc: the logits of up to ENSEMBLE_MAX models -> one fp32 row of combined log-probabilities."""
+    _c_name_ = "vct_ensemble_desc"
+    _fields_ = [("n", i32), ("mode", i32), ("rows", i32), ("V", i32), ("dtype", i32 * ENSEMBLE_MAX), ("x", vp * ENSEMBLE_MAX),
+                ("ld", i64 * ENSEMBLE_MAX), ("w", vp), ("out", vp), ("ld_out", i64)]
+
+
 CIDER_MAX_LEN, CIDER_MAX_ORDER = 64, 4
 
 
@@ -279,6 +290,7 @@ C_CONSTANTS = {
     "VCT_TEMPORAL_FIXED": TEMPORAL["encoding"], "VCT_TEMPORAL_LEARNED": TEMPORAL["embedding"],
     **_c("VCT_MATCH_", MATCH_LOSS), **_c("VCT_MATCH_TEMP_", MATCH_TEMP), **_c("VCT_RETRIEVAL_", RETRIEVAL_MODE),
     **_c("VCT_RETRIEVAL_PH_", RETRIEVAL_PHASE), **_c("VCT_DEC_PRO_", DEC_PRO),
+    "VCT_ENSEMBLE_MAX": ENSEMBLE_MAX, **_c("VCT_ENS_", ENS_MODE),
 }
 
 _SIGS = {
@@ -355,6 +367,7 @@ _SIGS = {
     "vct_sample_select_workspace_bytes": (i64, [C.c_int, C.c_int, C.c_int]),
     "vct_sample_select": (C.c_int, [C.POINTER(SampleSelectDesc), vp]),
     "vct_logit_controls": (C.c_int, [C.POINTER(LogitControlsDesc), vp]),
+    "vct_ensemble_combine": (C.c_int, [C.POINTER(EnsembleDesc), vp]),
     "vct_gather_pad_rows": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
     "vct_adam_step": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, i64, i64, i32, vp, vp]),
     "vct_adam_step_pk": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, vp, i64, i64, i32, vp, vp, C.c_int, i64, vp]),

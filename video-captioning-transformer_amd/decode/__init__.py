@@ -19,13 +19,17 @@ per video with their log-probabilities; the reference has none either, the seman
 
 Generation controls (`GenerationControls`, `apply_controls_host`): minimum length, no-repeat n-gram ban, repetition penalty and
 banned ids, applied to the step's logits on the device in front of the selection of all three decoders (`controls=`); the
-reference has none, the semantics are stated in `GenerationControls`."""
+reference has none, the semantics are stated in `GenerationControls`.
+
+Ensembles (`Ensemble`): several models behind one greedy / beam / sampled session, their next-token distributions averaged on the
+device at every step (decode/ensemble.py); the reference decodes with one checkpoint."""
 from ..engine import memory_len
 from .controls import (CONTROLS_BANNED_MAX, CONTROLS_MAX_LEN, CONTROLS_NGRAM_MAX, CONTROLS_THETA_MAX, GenerationControls, _f32,
                        _resolve_controls, apply_controls_host)
 from .rules import (SAMPLE_TOP_K_MAX, _beam_finish, _beam_size, _check_sample_args, _draw_seed, _hash32, _no_beam_attn,
                     sample_uniforms)
-from .cached import (_inputs_key, _run_session, _session, beam_decode_ids, greedy_decode_ids, sample_decode_ids,
+from .cached import (_inputs_key, _run_session, _session, _token_loop, beam_decode_ids, greedy_decode_ids, sample_decode_ids,
                      teacher_forced_next_ids)
+from .ensemble import ENSEMBLE_MAX, Ensemble, normalise_weights
 from .reference import (_sample_select_ref, _select_ref, beam_decode_ids_reference_algorithm,
                         greedy_decode_ids_reference_algorithm, sample_decode_ids_reference_algorithm)

@@ -60,12 +60,27 @@ def greedy_decode_ids(model, feats: torch.Tensor, mask, max_len: int = 30, use_g
 
 
 def _run_session(model, st, feats, mask, max_len, use_graphs, sync_every, lookahead) -> int:
-    """The token loop of every session, greedy, beam or sampled: prologue (encoder + begin), one captured graph per position, the
-    device-side stop word polled `lookahead` steps behind the launch front.  Returns the last step to keep."""
+    """The token loop of a single-model session, greedy, beam or sampled (_token_loop on this model's encoder and decoder).  Returns
+    the last step to keep."""
     pre = model.cap_preprocessor
     model._ps.refresh_shadow()
     model._ps.refresh_lazy_transposed()
     enc, dec = model.video_encoder._engine(), model.cap_decoder._engine()
+
+    def begin(fin, min_):
+        dec.decode_begin(st, enc.forward(fin, min_, False), pre.start_id, pre.pad_id)
+
+    def step(t):
+        dec.decode_step(st, t, pre.end_id)
+    return _token_loop(st, begin, step, lambda: model._ps.ctx.generation, feats, mask, max_len, use_graphs, sync_every, lookahead)
+
+
+def _token_loop(st, begin, step, generation, feats, mask, max_len, use_graphs, sync_every, lookahead) -> int:
+    """The token loop of every session: prologue, one captured graph per position, the device-side stop word polled `lookahead`
+    steps behind the launch front.  begin(feats, mask): the prologue (encoder forward + the session's start) on these inputs;
+    step(t): one token step; generation(): a value that moves whenever a buffer the prologue bakes has been re-allocated.  st: the
+    state that owns the graphs, the stop word (all_ended_at) and the polling objects -- an ensemble's leader.  Returns the last
+    step to keep."""
     on_gpu = _first(feats).device.type == "cuda"
     if on_gpu and st.poll_stream is None:
         st.poll_stream = torch.cuda.Stream(device=_first(feats).device)
@@ -77,26 +92,26 @@ def _run_session(model, st, feats, mask, max_len, use_graphs, sync_every, lookah
         # copies.  It bakes pointers into the engines' shared grow-only buffers: re-captured whenever any of them grew.
         key = _inputs_key(feats, mask)
         bg = st.begin
-        if bg is None or bg["key"] != key or bg["gen"] != model._ps.ctx.generation:
+        if bg is None or bg["key"] != key or bg["gen"] != generation():
             fin, min_ = static_inputs(feats, True), static_inputs(mask, True)
-            dec.decode_begin(st, enc.forward(fin, min_, False), pre.start_id, pre.pad_id)      # warm-up: allocates
+            begin(fin, min_)      # warm-up: allocates
             g = torch.cuda.CUDAGraph()
             with capture_graph(g):
-                dec.decode_begin(st, enc.forward(fin, min_, False), pre.start_id, pre.pad_id)
-            st.begin = {"key": key, "gen": model._ps.ctx.generation, "g": g, "fin": fin, "min": min_}
+                begin(fin, min_)
+            st.begin = {"key": key, "gen": generation(), "g": g, "fin": fin, "min": min_}
         else:
             stage_inputs(bg["fin"], feats)
             if mask is not None:
                 stage_inputs(bg["min"], mask)
             bg["g"].replay()
     else:
-        dec.decode_begin(st, enc.forward(feats, mask, False), pre.start_id, pre.pad_id)
+        begin(feats, mask)
     stop = max_len
 
-    def ended_as_of(step: int) -> int:
-        """all_ended_at once `step` has run (later steps may still be in flight: the word only ever decreases to the FIRST step
+    def ended_as_of(done: int) -> int:
+        """all_ended_at once step `done` has run (later steps may still be in flight: the word only ever decreases to the FIRST step
         at which every row had ended, so a value read early is either max_len or final)."""
-        st.events[step].synchronize()       # the HOST waits for that step (later steps stay queued on the device) ...
+        st.events[done].synchronize()       # the HOST waits for that step (later steps stay queued on the device) ...
         with torch.cuda.stream(st.poll_stream):
             # ... so the copy needs no device-side dependency: a cross-stream wait on an event that is still pending costs
             # ~0.8 ms of latency on this runtime (tools/decode_loop_probe2.py), an independent 8-byte copy 20 us
@@ -108,16 +123,16 @@ def _run_session(model, st, feats, mask, max_len, use_graphs, sync_every, lookah
         if use_graphs:
             g = st.graphs.get(t)
             if g is None:
-                dec.decode_step(st, t, pre.end_id)         # warm-up run (allocates the step's temporaries)
+                step(t)                                    # warm-up run (allocates the step's temporaries)
                 # the warm-up already wrote ys[:, t]; capture replays the same work
                 g = torch.cuda.CUDAGraph()
                 with capture_graph(g):
-                    dec.decode_step(st, t, pre.end_id)
+                    step(t)
                 st.graphs[t] = g
             else:
                 g.replay()
         else:
-            dec.decode_step(st, t, pre.end_id)
+            step(t)
         if not on_gpu:
             continue
         if t % sync_every == 0 or t == max_len - 1:

@@ -9,7 +9,8 @@ from ._common import Drop
 from .attention import attn_bwd, attn_fwd, attn_weights
 from .clip import grad_clip_apply, grad_segments_table, grad_sqnorm, grad_sqnorm_scratch
 from .decoding import (beam_reorder, beam_select, beam_select_workspace_bytes, decode_block, decode_block_supported, decode_gemv,
-                       decode_linear, decode_ln2, greedy_select, logit_controls, sample_select, sample_select_workspace_bytes)
+                       decode_linear, decode_ln2, ensemble_combine, greedy_select, logit_controls, sample_select,
+                       sample_select_workspace_bytes)
 from .elementwise import advance_seed, argmax_rows, axpby, cast, gather_pad_rows, scale, transpose, warm
 from .embed import embed_bwd, embed_fwd, embed_live_rebuild, embed_live_table, text_pool
 from .frontend import (enc_frontend_bwd, enc_frontend_ex_bwd, enc_frontend_ex_fwd, enc_frontend_fwd, hmm_mix_bwd, hmm_mix_fwd,

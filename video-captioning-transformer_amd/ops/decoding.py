@@ -1,5 +1,5 @@
 """Caption decoding: greedy / beam / sampled selection and the KV-cached decode-step kernels (csrc/vct_decode.hip,
-csrc/vct_decode_block.hip, csrc/vct_beam.hip, csrc/vct_sample.hip, csrc/vct_logit_controls.hip)."""
+csrc/vct_decode_block.hip, csrc/vct_beam.hip, csrc/vct_sample.hip, csrc/vct_logit_controls.hip, csrc/vct_ensemble.hip)."""
 import torch
 
 from .. import _lib as L
@@ -70,6 +70,26 @@ def logit_controls(x, ids, ended, ctl, t: int, end_id: int, cols=None, parents=N
         d.parents, d.parents_stride, d.K = parents.data_ptr(), parents.stride(0), int(K)
     L.check(L.load().vct_logit_controls(L.C.byref(d), L.stream_ptr()), "vct_logit_controls")
     return x
+
+
+def ensemble_combine(xs, w, out, mode: str = "prob", cols=None):
+    """The members' logits of one decode step -> one fp32 row of combined log-probabilities per row (include/vct_hip.h,
+    vct_ensemble_combine).  xs: 1..8 tensors [rows, ld_m] (fp32 or bf16, mixed freely); w: DEVICE fp32 [8], normalised by the
+    host (a member with weight 0 is skipped); out: fp32 [rows, ld_out]; mode "prob" (arithmetic mean of the probabilities) or
+    "logp" (weighted sum of the log-probabilities).  Columns >= cols are neither read nor written."""
+    if not 1 <= len(xs) <= L.ENSEMBLE_MAX:
+        raise ValueError(f"ensemble_combine: {len(xs)} members (1..{L.ENSEMBLE_MAX})")
+    if w.dtype != torch.float32 or w.numel() < L.ENSEMBLE_MAX or out.dtype != torch.float32:
+        raise TypeError("ensemble_combine: w is fp32 [8] and out fp32")
+    d = L.EnsembleDesc()
+    d.n, d.mode, d.rows, d.V = len(xs), L.ENS_MODE[mode], out.shape[0], int(cols or out.shape[1])
+    for m, x in enumerate(xs):
+        if x.shape[0] != out.shape[0]:
+            raise ValueError("ensemble_combine: every member has out's rows")
+        d.dtype[m], d.x[m], d.ld[m] = L.dtype_code(x.dtype), x.data_ptr(), _ld(x)
+    d.w, d.out, d.ld_out = w.data_ptr(), out.data_ptr(), _ld(out)
+    L.check(L.load().vct_ensemble_combine(L.C.byref(d), L.stream_ptr()), "vct_ensemble_combine")
+    return out
 
 
 def decode_gemv(W, out, B, *, bias=None, pro="none", x_in=None, ln1=None, ln2=None, embed=None, attn=None, act=None, res=None,
