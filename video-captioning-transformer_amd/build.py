@@ -9,7 +9,7 @@ import subprocess
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libvct_hip.so")
-SOURCES = ["vct_gemm.hip", "vct_gemm_bf16.hip", "vct_gemm_bf16_nt.hip", "vct_gemm_bf16_nn.hip", "vct_gemm_bf16_tn.hip", "vct_gemm256.hip", "vct_gemm_pt.hip", "vct_gemm_skinny.hip", "vct_attn.hip", "vct_attn_weights.hip", "vct_layer_ss.hip", "vct_layer_ss_bwd.hip", "vct_norm.hip", "vct_elem.hip", "vct_caption_loss.hip", "vct_cider.hip", "vct_capmetric.hip", "vct_optim.hip", "vct_grad_clip.hip", "vct_decode.hip", "vct_decode_block.hip", "vct_beam.hip", "vct_sample.hip", "vct_logit_controls.hip", "vct_ensemble.hip", "vct_mm_frontend.hip", "vct_enc_frontend_ex.hip", "vct_hmm_mix.hip", "vct_match.hip", "vct_retrieval.hip", "vct_text.hip", "vct_vision.hip", "vct_runtime.hip", "vct_comm.hip"]
+SOURCES = ["vct_gemm.hip", "vct_gemm_bf16.hip", "vct_gemm_bf16_nt.hip", "vct_gemm_bf16_nn.hip", "vct_gemm_bf16_tn.hip", "vct_gemm256.hip", "vct_gemm_pt.hip", "vct_gemm_skinny.hip", "vct_attn.hip", "vct_attn_weights.hip", "vct_layer_ss.hip", "vct_layer_ss_bwd.hip", "vct_norm.hip", "vct_elem.hip", "vct_caption_loss.hip", "vct_cider.hip", "vct_capmetric.hip", "vct_optim.hip", "vct_grad_clip.hip", "vct_decode.hip", "vct_decode_block.hip", "vct_select.hip", "vct_beam.hip", "vct_sample.hip", "vct_logit_controls.hip", "vct_ensemble.hip", "vct_mm_frontend.hip", "vct_enc_frontend_ex.hip", "vct_hmm_mix.hip", "vct_match.hip", "vct_retrieval.hip", "vct_text.hip", "vct_vision.hip", "vct_runtime.hip", "vct_comm.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"]
 
 

@@ -17,114 +17,39 @@
 // A row's contribution to the top K is among its own top-K logits: s[k] + (x - lse[k]) is monotone in x.  (Two distinct
 // logits that round to the same value would be ranked by logit, not by flat index: the documented fp32 exception.)
 // The two stages are two launches, so no inter-workgroup hand-off inside a launch: the partials reach stage 2 through the
-// kernel boundary.
+// kernel boundary.  The tie rule, the chunk scan of stage 1, the arg-max reductions and the stop bookkeeping are
+// vct_select_core.h's, shared with vct_select.hip and vct_sample.hip.
 //
 // vct_beam_reorder, one launch for every layer: slot s < t of row j of the other cache of a ping-pong pair <- slot s of row
 // parent[j] (columns [d, 3d): k | v; q is only ever read at the current slot), whole 16-byte units where the row allows.
-#include "vct_common.h"
+#include "vct_select_core.h"
 
 namespace vct {
 
-constexpr int BEAM_THREADS = 256;
-constexpr int BEAM_NONE = 0x7fffffff;       // empty entry: loses to every real candidate, -inf valued ones included
-
-__device__ __forceinline__ bool beam_better(float av, int ai, float bv, int bi) {
-  return av > bv || (av == bv && ai < bi);
-}
-
-// (value, index) arg-max over the 64 lanes of a wave, ties to the smaller index
-__device__ __forceinline__ void beam_wave_best(float& v, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(v, o);
-    const int oi = __shfl_xor(i, o);
-    if (beam_better(ov, oi, v, i)) { v = ov; i = oi; }
-  }
-}
-
-// workgroup arg-max of every thread's (v, i); the LDS buffer is double-buffered by round parity, so one barrier per round
-__device__ __forceinline__ void beam_block_best(float& v, int& i, float (*s_v)[BEAM_THREADS / 64], int (*s_i)[BEAM_THREADS / 64],
-                                                int round) {
-  beam_wave_best(v, i);
-  const int w = threadIdx.x >> 6, p = round & 1;
-  if ((threadIdx.x & 63) == 0) { s_v[p][w] = v; s_i[p][w] = i; }
-  __syncthreads();
-  v = s_v[p][0]; i = s_i[p][0];
-#pragma unroll
-  for (int u = 1; u < BEAM_THREADS / 64; u++)
-    if (beam_better(s_v[p][u], s_i[p][u], v, i)) { v = s_v[p][u]; i = s_i[p][u]; }
-}
+constexpr int BEAM_THREADS = SEL_THREADS;
 
 template <typename T>
 __global__ __launch_bounds__(BEAM_THREADS) void beam_partial_kernel(int V, int K, const T* __restrict__ x, int64_t ldx, bool vec_ok,
                                                                     float* __restrict__ pmax, float* __restrict__ psum,
                                                                     float* __restrict__ ptv, int* __restrict__ pti) {
   constexpr int VEC = 16 / (int)sizeof(T);
-  constexpr int CHUNK = BEAM_THREADS * VEC;
-  __shared__ float s_v[2][BEAM_THREADS / 64];
-  __shared__ int s_i[2][BEAM_THREADS / 64];
+  __shared__ float s_v[2][SEL_WAVES];
+  __shared__ int s_i[2][SEL_WAVES];
+  __shared__ float s_sum[SEL_WAVES];
   const int chunk = blockIdx.x, CH = gridDim.x, row = blockIdx.y;
-  const T* r = x + (size_t)row * ldx;
-  const int c0 = chunk * CHUNK + threadIdx.x * VEC;
   float e[VEC];
   int id[VEC];
-  if (vec_ok && c0 + VEC <= V) {
-    struct alignas(16) Vt { T e[VEC]; };
-    const Vt w = *reinterpret_cast<const Vt*>(r + c0);
-#pragma unroll
-    for (int u = 0; u < VEC; u++) { e[u] = to_f<T>(w.e[u]); id[u] = c0 + u; }
-  } else {
-#pragma unroll
-    for (int u = 0; u < VEC; u++) {
-      const bool in = c0 + u < V;
-      e[u] = in ? to_f<T>(r[c0 + u]) : -INFINITY;
-      id[u] = in ? c0 + u : BEAM_NONE;
-    }
-  }
-  // chunk max and sum of exp(x - max)
-  float hv = -INFINITY;
-  int hi = BEAM_NONE;
-#pragma unroll
-  for (int u = 0; u < VEC; u++)
-    if (beam_better(e[u], id[u], hv, hi)) { hv = e[u]; hi = id[u]; }
-  float mv = hv;
-  int mi = hi;
-  beam_block_best(mv, mi, s_v, s_i, 0);
-  float se = 0.0f;
-  if (mv != -INFINITY) {
-#pragma unroll
-    for (int u = 0; u < VEC; u++) se += (id[u] != BEAM_NONE) ? expf(e[u] - mv) : 0.0f;
-  }
-  __shared__ float s_sum[BEAM_THREADS / 64];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o);
-  if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = se;
-  __syncthreads();
+  sel_chunk_load<T, VEC>(x + (size_t)row * ldx, (chunk * BEAM_THREADS + threadIdx.x) * VEC, V, vec_ok, e, id);
+  float hv, mv;
+  int hi, mi;
+  sel_head(e, id, hv, hi);
+  mv = hv; mi = hi;
+  sel_block_best<SEL_WAVES>(mv, mi, s_v, s_i, 0);
+  // chunk max and sum of exp(x - max); a chunk without a finite logit sums to 0
+  const float se = sel_chunk_expsum(e, id, 1.0f, mv, s_sum);
   const size_t pc = (size_t)row * CH + chunk;
-  if (threadIdx.x == 0) {
-    float t = 0.0f;
-#pragma unroll
-    for (int w = 0; w < BEAM_THREADS / 64; w++) t += s_sum[w];
-    pmax[pc] = mv;
-    psum[pc] = t;
-  }
-  // top K of the chunk: round 0's winner is the max found above
-  for (int k = 0; k < K; k++) {
-    float bv = hv;
-    int bi = hi;
-    if (k > 0) beam_block_best(bv, bi, s_v, s_i, k);
-    else { bv = mv; bi = mi; }
-    if (threadIdx.x == 0) { ptv[pc * K + k] = bv; pti[pc * K + k] = bi; }
-    if (bi == hi && bi != BEAM_NONE) {          // the owner drops the element and finds its next head
-#pragma unroll
-      for (int u = 0; u < VEC; u++)
-        if (id[u] == bi) { id[u] = BEAM_NONE; e[u] = -INFINITY; }
-      hv = -INFINITY; hi = BEAM_NONE;
-#pragma unroll
-      for (int u = 0; u < VEC; u++)
-        if (beam_better(e[u], id[u], hv, hi)) { hv = e[u]; hi = id[u]; }
-    }
-  }
+  if (threadIdx.x == 0) { pmax[pc] = mv; psum[pc] = mv != -INFINITY ? se : 0.0f; }
+  sel_chunk_topk(K, e, id, hv, hi, mv, mi, s_v, s_i, ptv, pti, pc, K);
 }
 
 // sorted (descending, ties by index) register list of a thread's best KMAX candidates; compile-time indices only
@@ -134,15 +59,15 @@ struct BeamList {
   int i[KMAX];
   __device__ __forceinline__ void init() {
 #pragma unroll
-    for (int p = 0; p < KMAX; p++) { v[p] = -INFINITY; i[p] = BEAM_NONE; }
+    for (int p = 0; p < KMAX; p++) { v[p] = -INFINITY; i[p] = SEL_NONE; }
   }
   __device__ __forceinline__ void insert(float nv, int ni) {
-    if (!beam_better(nv, ni, v[KMAX - 1], i[KMAX - 1])) return;
+    if (!sel_better(nv, ni, v[KMAX - 1], i[KMAX - 1])) return;
     bool placed = false;
 #pragma unroll
     for (int p = KMAX - 1; p > 0; p--) {
       if (!placed) {
-        if (beam_better(nv, ni, v[p - 1], i[p - 1])) { v[p] = v[p - 1]; i[p] = i[p - 1]; }
+        if (sel_better(nv, ni, v[p - 1], i[p - 1])) { v[p] = v[p - 1]; i[p] = i[p - 1]; }
         else { v[p] = nv; i[p] = ni; placed = true; }
       }
     }
@@ -151,7 +76,7 @@ struct BeamList {
   __device__ __forceinline__ void pop() {
 #pragma unroll
     for (int p = 0; p < KMAX - 1; p++) { v[p] = v[p + 1]; i[p] = i[p + 1]; }
-    v[KMAX - 1] = -INFINITY; i[KMAX - 1] = BEAM_NONE;
+    v[KMAX - 1] = -INFINITY; i[KMAX - 1] = SEL_NONE;
   }
 };
 
@@ -166,8 +91,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_merge_kernel(int K, int V, 
   __shared__ uint8_t s_f[KMAX];
   __shared__ float s_wv[KMAX];
   __shared__ int s_wi[KMAX];
-  __shared__ float s_v[2][BEAM_THREADS / 64];
-  __shared__ int s_i[2][BEAM_THREADS / 64];
+  __shared__ float s_v[2][SEL_WAVES];
+  __shared__ int s_i[2][SEL_WAVES];
   const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int row0 = b * K;
   if (threadIdx.x < K) {
@@ -175,7 +100,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_merge_kernel(int K, int V, 
     s_f[threadIdx.x] = finished[row0 + threadIdx.x];
   }
   // logsumexp of each row: one wave per row, lanes over the chunks, fixed reduction order
-  for (int k = w; k < K; k += BEAM_THREADS / 64) {
+  for (int k = w; k < K; k += SEL_WAVES) {
     const size_t base = (size_t)(row0 + k) * CH;
     float m = -INFINITY;
     for (int c = lane; c < CH; c += 64) m = fmaxf(m, pmax[base + c]);
@@ -204,15 +129,15 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_merge_kernel(int K, int V, 
     }
     const size_t e = (size_t)row0 * per_row + it;
     const int col = pti[e];
-    if (col == BEAM_NONE) continue;
+    if (col == SEL_NONE) continue;
     const float logp = ptv[e] - s_lse[k];
     lst.insert(s_s[k] + logp, k * V + col);
   }
   for (int r = 0; r < K; r++) {
     float bv = lst.v[0];
     int bi = lst.i[0];
-    beam_block_best(bv, bi, s_v, s_i, r);
-    if (bi == lst.i[0] && bi != BEAM_NONE) lst.pop();
+    sel_block_best<SEL_WAVES>(bv, bi, s_v, s_i, r);
+    if (bi == lst.i[0] && bi != SEL_NONE) lst.pop();
     if (threadIdx.x == 0) { s_wv[r] = bv; s_wi[r] = bi; }
   }
   __syncthreads();
@@ -229,8 +154,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_merge_kernel(int K, int V, 
       finished[j] = nf ? 1 : 0;
     }
     const int n = __popcll(__ballot(nf));
-    // the step's finished slots over all videos: integer atomics only, the result does not depend on arrival order
-    if (lane == 0 && n > 0 && atomicAdd(finished_count, n) + n == M) atomicMin(all_finished_at, (unsigned long long)t);
+    if (lane == 0) sel_mark_ended(nullptr, n, finished_count, M, all_finished_at, t);   // the step's finished slots over all videos
   }
 }
 
@@ -250,13 +174,6 @@ __global__ __launch_bounds__(64) void beam_reorder_kernel(int M, int Lmax, int t
 
 }  // namespace vct
 using namespace vct;
-
-static bool dt_ok_beam(int dt) { return dt == VCT_F32 || dt == VCT_BF16; }
-
-static size_t beam_chunks(int dtype, int V) {
-  const int chunk = BEAM_THREADS * (dtype == VCT_BF16 ? 8 : 4);
-  return (size_t)((V + chunk - 1) / chunk);
-}
 
 template <int KMAX>
 static void beam_launch(int dtype, int B, int K, int V, const void* x, int64_t ldx, bool vec_ok, float* pmax, float* psum,
@@ -278,12 +195,12 @@ extern "C" int vct_beam_select(int dtype, int B, int K, int V, const void* x, in
                                int32_t* parent, int64_t* out, int64_t out_stride, int64_t end_id, int64_t pad_id,
                                int32_t* finished_count, int64_t* all_finished_at, int32_t t, void* workspace,
                                int64_t workspace_bytes, void* stream) {
-  if (!dt_ok_beam(dtype) || !x || !scores || !finished || !parent || !out || !finished_count || !all_finished_at || !workspace)
+  if (!dt_ok(dtype) || !x || !scores || !finished || !parent || !out || !finished_count || !all_finished_at || !workspace)
     return VCT_E_ARG;
   if (K < 1 || K > 16 || B <= 0 || V <= 0 || K > V || ldx < V || out_stride <= 0 || t < 0) return VCT_E_SHAPE;
   if (pad_id < 0 || pad_id >= V) return VCT_E_ARG;
-  if ((int64_t)B * K > 65535 || (int64_t)K * V >= (int64_t)BEAM_NONE) return VCT_E_SHAPE;
-  const size_t CH = beam_chunks(dtype, V);
+  if ((int64_t)B * K > 65535 || (int64_t)K * V >= (int64_t)SEL_NONE) return VCT_E_SHAPE;
+  const size_t CH = (size_t)sel_chunks(dtype, V);
   const size_t MC = (size_t)B * K * CH;
   if ((size_t)workspace_bytes < MC * (2 + 2 * (size_t)K) * 4) return VCT_E_WORKSPACE;
   float* pmax = (float*)workspace;
@@ -309,7 +226,7 @@ extern "C" int vct_beam_select(int dtype, int B, int K, int V, const void* x, in
 
 extern "C" int vct_beam_reorder(int dtype, int L, int M, int Lmax, int d, int t, const int32_t* parent, const void* src, void* dst,
                                 int64_t layer_stride, void* stream) {
-  if (!dt_ok_beam(dtype) || !parent || !src || !dst) return VCT_E_ARG;
+  if (!dt_ok(dtype) || !parent || !src || !dst) return VCT_E_ARG;
   if (L <= 0 || M <= 0 || Lmax <= 0 || d <= 0 || t < 1 || t > Lmax) return VCT_E_SHAPE;
   if (layer_stride < (int64_t)M * Lmax * 3 * d) return VCT_E_SHAPE;
   if ((int64_t)L * M * t > 0x7fffffffLL) return VCT_E_SHAPE;

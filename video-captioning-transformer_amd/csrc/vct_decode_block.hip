@@ -16,7 +16,7 @@
 // workgroup of the CONSUMING launch sums them in its prologue, in index order (deterministic), together with the residual, the
 // bias and the LayerNorm(s) -- 16-64 KB of L2 reads per workgroup, a few dozen workgroups.  Activations between launches are fp32
 // vectors; q / k / v are rounded to bf16 where they enter the cache (what the later steps and the batched kernels read).
-#include "vct_common.h"
+#include "vct_select_core.h"
 
 namespace vct {
 
@@ -378,16 +378,10 @@ __global__ __launch_bounds__(DB_THREADS) void decode_gen_kernel(const DbP p) {
   if (p.sel_ws == nullptr) return;
   // ---- greedy selection (MMT4Caption.py:166-171; torch.max: the FIRST maximal index): workgroup arg-max -> (value, index) pair
   // written through the L2 -> ticket; the last workgroup reduces the pairs.  The separate arg-max launch over the 122 KB of
-  // logits cost 6.7 us per token.  Same comparison as argmax_rows_kernel: larger value, then smaller index.
+  // logits cost 6.7 us per token.  The comparison and the wave arg-max are vct_select_core.h's, as argmax_rows_kernel's.
   float bv = have ? mine : -INFINITY;
-  int bi = have ? n : 0x7fffffff;
-  auto better = [](float v, int i, float bv_, int bi_) { return v > bv_ || (v == bv_ && i < bi_); };
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(bv, o);
-    const int oi = __shfl_xor(bi, o);
-    if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-  }
+  int bi = have ? n : SEL_NONE;
+  sel_wave_best(bv, bi);
   __shared__ float s_v[DB_WAVES];
   __shared__ int s_i[DB_WAVES];
   __shared__ int s_last;
@@ -395,8 +389,7 @@ __global__ __launch_bounds__(DB_THREADS) void decode_gen_kernel(const DbP p) {
   __syncthreads();
   int* ticket = reinterpret_cast<int*>(p.sel_ws + 2 * gridDim.x);
   if (tid == 0) {
-#pragma unroll
-    for (int w = 1; w < DB_WAVES; w++) if (better(s_v[w], s_i[w], bv, bi)) { bv = s_v[w]; bi = s_i[w]; }
+    sel_fold_waves<DB_WAVES>(bv, bi, s_v, s_i);
     typedef __attribute__((ext_vector_type(2))) float f32x2;
     const f32x2 pr = {bv, __int_as_float(bi)};
     __hip_atomic_store(reinterpret_cast<unsigned long long*>(p.sel_ws + 2 * blockIdx.x), __builtin_bit_cast(unsigned long long, pr),
@@ -408,33 +401,25 @@ __global__ __launch_bounds__(DB_THREADS) void decode_gen_kernel(const DbP p) {
   }
   __syncthreads();
   if (!s_last) return;
-  bv = -INFINITY; bi = 0x7fffffff;
+  bv = -INFINITY; bi = SEL_NONE;
   for (int g = tid; g < (int)gridDim.x; g += DB_THREADS) {
     typedef __attribute__((ext_vector_type(2))) float f32x2;
     const unsigned long long u = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p.sel_ws + 2 * g), __ATOMIC_RELAXED,
                                                    __HIP_MEMORY_SCOPE_AGENT);
     const f32x2 pr = __builtin_bit_cast(f32x2, u);
     const int gi = __float_as_int(pr[1]);
-    if (better(pr[0], gi, bv, bi)) { bv = pr[0]; bi = gi; }
+    if (sel_better(pr[0], gi, bv, bi)) { bv = pr[0]; bi = gi; }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(bv, o);
-    const int oi = __shfl_xor(bi, o);
-    if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-  }
+  sel_wave_best(bv, bi);
   __syncthreads();                                       // s_v / s_i of the first reduction have been read
   if (lane == 0) { s_v[wave] = bv; s_i[wave] = bi; }
   __syncthreads();
   if (tid == 0) {
-#pragma unroll
-    for (int w = 1; w < DB_WAVES; w++) if (better(s_v[w], s_i[w], bv, bi)) { bv = s_v[w]; bi = s_i[w]; }
-    const int tok = (bi == 0x7fffffff) ? 0 : bi;
+    sel_fold_waves<DB_WAVES>(bv, bi, s_v, s_i);
+    const int tok = (bi == SEL_NONE) ? 0 : bi;
     p.tok_out[0] = tok;
-    if (p.ended != nullptr && tok == p.end_id && !p.ended[0]) {      // one caption: it completes the set by itself
-      p.ended[0] = 1;
-      if (atomicAdd(p.ended_count, 1) + 1 == 1) atomicMin(p.all_ended_at, (unsigned long long)p.t);
-    }
+    if (p.ended != nullptr && tok == p.end_id && !p.ended[0])        // one caption: it completes the set by itself
+      sel_mark_ended(&p.ended[0], 1, p.ended_count, 1, p.all_ended_at, p.t);
     __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // ready for the next token
   }
 }

@@ -1,6 +1,6 @@
 // HBM-bound pieces of the caption path on gfx950: encoder front end (mean token + temporal
-// encoding), token embedding gather / deterministic scatter-add, casts, first-index arg-max,
-// dropout seed advance (the caption losses: vct_caption_loss.hip).  All loads/stores are 16-byte vectors where the
+// encoding), token embedding gather / deterministic scatter-add, casts, dropout seed advance
+// (the caption losses: vct_caption_loss.hip; the first-index arg-max: vct_select.hip).  All loads/stores are 16-byte vectors where the
 // layout allows; reductions use wave shuffles + a few LDS words.
 #include "vct_common.h"
 
@@ -383,59 +383,6 @@ __global__ __launch_bounds__(256) void gather_pad_rows_kernel(const float* __res
   for (int i = e4 * 4 + lane; i < E; i += 64) dst[i] = from_f<TD>(src[i]);
 }
 
-constexpr int AMX_THREADS = 1024;
-template <typename T>
-__global__ __launch_bounds__(AMX_THREADS) void argmax_rows_kernel(int cols, const T* __restrict__ x, int64_t ldx,
-                                                          int64_t* __restrict__ out, int64_t out_stride,
-                                                          int64_t end_id, uint8_t* __restrict__ ended,
-                                                          int32_t* __restrict__ ended_count,
-                                                          unsigned long long* __restrict__ all_ended_at, int t) {
-  __shared__ float s_v[AMX_THREADS / 64];
-  __shared__ int s_i[AMX_THREADS / 64];
-  const T* r = x + (size_t)blockIdx.x * ldx;
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
-  // 16-byte loads when the row allows it (a 30522-column row is 4 vector loads per thread instead of 30 scalar round trips:
-  // the one-workgroup-per-row scan took 37 us per decoded token)
-  constexpr int VEC = 16 / (int)sizeof(T);
-  const bool vec_ok = (((uintptr_t)r) & 15) == 0;
-  const int nv = vec_ok ? cols / VEC : 0;
-  struct alignas(16) V { T e[VEC]; };
-  for (int j = threadIdx.x; j < nv; j += AMX_THREADS) {
-    const V v = reinterpret_cast<const V*>(r)[j];
-#pragma unroll
-    for (int u = 0; u < VEC; u++) {
-      const float f = to_f<T>(v.e[u]);
-      const int c = j * VEC + u;
-      if (f > best || (f == best && c < bi)) { best = f; bi = c; }
-    }
-  }
-  for (int j = nv * VEC + threadIdx.x; j < cols; j += AMX_THREADS) {
-    const float v = to_f<T>(r[j]);
-    if (v > best || (v == best && j < bi)) { best = v; bi = j; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o);
-    const int oi = __shfl_xor(bi, o);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
-  if ((threadIdx.x & 63) == 0) { s_v[threadIdx.x >> 6] = best; s_i[threadIdx.x >> 6] = bi; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < AMX_THREADS / 64; w++)
-      if (s_v[w] > best || (s_v[w] == best && s_i[w] < bi)) { best = s_v[w]; bi = s_i[w]; }
-    const int tok = (bi == 0x7fffffff) ? 0 : bi;
-    out[(size_t)blockIdx.x * out_stride] = tok;
-    // greedy-decode bookkeeping (MMT4Caption.py:166-171): sticky per-row end flag; the row that completes the set
-    // records the step.  Integer atomics only: the result does not depend on arrival order.
-    if (ended != nullptr && tok == end_id && !ended[blockIdx.x]) {
-      ended[blockIdx.x] = 1;
-      if (atomicAdd(ended_count, 1) + 1 == (int)gridDim.x) atomicMin(all_ended_at, (unsigned long long)t);
-    }
-  }
-}
-
 __global__ void advance_seed_kernel(uint32_t* seed) { seed[0] += 1u; }
 
 }  // namespace vct
@@ -605,38 +552,6 @@ extern "C" int vct_cast(int src_dtype, int dst_dtype, const void* src, void* dst
     vct::launch((cast_kernel<float, float>), dim3(blocks), dim3(256), 0, st, (const float*)src, (float*)dst, n);
   else
     vct::launch((cast_kernel<bf16_t, bf16_t>), dim3(blocks), dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, n);
-  VCT_CHECK_LAUNCH();
-  return VCT_OK;
-}
-
-extern "C" int vct_argmax_rows(int dtype, int rows, int cols, const void* x, int64_t ldx, int64_t* out, int64_t out_stride,
-                               void* stream) {
-  if (!dt_ok(dtype) || !x || !out) return VCT_E_ARG;
-  if (rows <= 0 || cols <= 0 || out_stride <= 0) return VCT_E_SHAPE;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == VCT_BF16)
-    vct::launch((argmax_rows_kernel<bf16_t>), dim3(rows), dim3(AMX_THREADS), 0, st, cols, (const bf16_t*)x, ldx, out, out_stride,
-                       (int64_t)0, (uint8_t*)nullptr, (int32_t*)nullptr, (unsigned long long*)nullptr, 0);
-  else
-    vct::launch((argmax_rows_kernel<float>), dim3(rows), dim3(AMX_THREADS), 0, st, cols, (const float*)x, ldx, out, out_stride,
-                       (int64_t)0, (uint8_t*)nullptr, (int32_t*)nullptr, (unsigned long long*)nullptr, 0);
-  VCT_CHECK_LAUNCH();
-  return VCT_OK;
-}
-
-extern "C" int vct_greedy_select(int dtype, int rows, int cols, const void* x, int64_t ldx, int64_t* out, int64_t out_stride,
-                                 int64_t end_id, uint8_t* ended, int32_t* ended_count, int64_t* all_ended_at, int32_t t,
-                                 void* stream) {
-  if (!dt_ok(dtype) || !x || !out || !ended || !ended_count || !all_ended_at) return VCT_E_ARG;
-  if (rows <= 0 || cols <= 0 || out_stride <= 0 || t < 0) return VCT_E_SHAPE;
-  hipStream_t st = (hipStream_t)stream;
-  unsigned long long* at = reinterpret_cast<unsigned long long*>(all_ended_at);
-  if (dtype == VCT_BF16)
-    vct::launch((argmax_rows_kernel<bf16_t>), dim3(rows), dim3(AMX_THREADS), 0, st, cols, (const bf16_t*)x, ldx, out, out_stride,
-                       end_id, ended, ended_count, at, (int)t);
-  else
-    vct::launch((argmax_rows_kernel<float>), dim3(rows), dim3(AMX_THREADS), 0, st, cols, (const float*)x, ldx, out, out_stride,
-                       end_id, ended, ended_count, at, (int)t);
   VCT_CHECK_LAUNCH();
   return VCT_OK;
 }

@@ -17,39 +17,17 @@
 //            nucleus cut and draw are wave operations over those <= 64 lanes.
 // Reductions and scans have a fixed order (shuffle trees, then a sequential pass over the waves / chunks): no floating-point
 // atomics, a second call is bit-identical.  Integer atomics only for the end bookkeeping, as vct_greedy_select.
-#include "vct_common.h"
+// The tie rule, the chunk scan of stage 1, the arg-max reductions and the end bookkeeping are vct_select_core.h's, shared with
+// vct_select.hip and vct_beam.hip.
+#include "vct_select_core.h"
 
 namespace vct {
 
-constexpr int SMP_THREADS = 256;
-constexpr int SMP_WAVES = SMP_THREADS / 64;
+constexpr int SMP_THREADS = SEL_THREADS;
+constexpr int SMP_WAVES = SEL_WAVES;
 constexpr int SMP_KMAX = 64;                // one candidate per lane of the merging wave
 constexpr int SMP_CHMAX = 64;               // one chunk list per lane of the merging wave
-constexpr int SMP_NONE = 0x7fffffff;        // empty entry: loses to every real candidate
 constexpr uint32_t SMP_SITE = 997u;         // the counter hash's site (engine/stack.py, SAMPLE_SITE)
-
-__device__ __forceinline__ bool smp_better(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai < bi); }
-
-__device__ __forceinline__ void smp_wave_best(float& v, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(v, o);
-    const int oi = __shfl_xor(i, o);
-    if (smp_better(ov, oi, v, i)) { v = ov; i = oi; }
-  }
-}
-
-// workgroup arg-max of every thread's (v, i); the LDS buffer is double-buffered by round parity: one barrier per round
-__device__ __forceinline__ void smp_block_best(float& v, int& i, float (*s_v)[SMP_WAVES], int (*s_i)[SMP_WAVES], int round) {
-  smp_wave_best(v, i);
-  const int w = threadIdx.x >> 6, p = round & 1;
-  if ((threadIdx.x & 63) == 0) { s_v[p][w] = v; s_i[p][w] = i; }
-  __syncthreads();
-  v = s_v[p][0]; i = s_i[p][0];
-#pragma unroll
-  for (int u = 1; u < SMP_WAVES; u++)
-    if (smp_better(s_v[p][u], s_i[p][u], v, i)) { v = s_v[p][u]; i = s_i[p][u]; }
-}
 
 // inclusive prefix sum over the 64 lanes (Hillis-Steele: a fixed order)
 __device__ __forceinline__ float smp_wave_scan(float v, int lane) {
@@ -63,24 +41,6 @@ __device__ __forceinline__ float smp_wave_scan(float v, int lane) {
 
 __device__ __forceinline__ int smp_clamp_k(int k, int V) { return k < 0 ? 0 : (k > SMP_KMAX ? min(SMP_KMAX, V) : min(k, V)); }
 
-// the chunk's elements of this thread: values (fp32) and columns (SMP_NONE past V)
-template <typename T, int VEC>
-__device__ __forceinline__ void smp_load(const T* __restrict__ r, int c0, int V, bool vec_ok, float (&e)[VEC], int (&id)[VEC]) {
-  if (vec_ok && c0 + VEC <= V) {
-    struct alignas(16) Vt { T e[VEC]; };
-    const Vt w = *reinterpret_cast<const Vt*>(r + c0);
-#pragma unroll
-    for (int u = 0; u < VEC; u++) { e[u] = to_f<T>(w.e[u]); id[u] = c0 + u; }
-  } else {
-#pragma unroll
-    for (int u = 0; u < VEC; u++) {
-      const bool in = c0 + u < V;
-      e[u] = in ? to_f<T>(r[c0 + u]) : -INFINITY;
-      id[u] = in ? c0 + u : SMP_NONE;
-    }
-  }
-}
-
 template <typename T>
 __global__ __launch_bounds__(SMP_THREADS) void sample_partial_kernel(int V, const T* __restrict__ x, int64_t ldx, bool vec_ok,
                                                                      const uint8_t* __restrict__ ended,
@@ -88,7 +48,6 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_partial_kernel(int V, cons
                                                                      float* __restrict__ psum, float* __restrict__ ptv,
                                                                      int* __restrict__ pti) {
   constexpr int VEC = 16 / (int)sizeof(T);
-  constexpr int CHUNK = SMP_THREADS * VEC;
   __shared__ float s_v[2][SMP_WAVES];
   __shared__ int s_i[2][SMP_WAVES];
   __shared__ float s_sum[SMP_WAVES];
@@ -98,51 +57,20 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_partial_kernel(int V, cons
   const float inv_temp = ctl->inv_temp;
   float e[VEC];
   int id[VEC];
-  smp_load<T, VEC>(x + (size_t)row * ldx, chunk * CHUNK + threadIdx.x * VEC, V, vec_ok, e, id);
-  float hv = -INFINITY;
-  int hi = SMP_NONE;
-#pragma unroll
-  for (int u = 0; u < VEC; u++)
-    if (smp_better(e[u], id[u], hv, hi)) { hv = e[u]; hi = id[u]; }
-  float mv = hv;
-  int mi = hi;
-  smp_block_best(mv, mi, s_v, s_i, 0);
+  sel_chunk_load<T, VEC>(x + (size_t)row * ldx, (chunk * SMP_THREADS + threadIdx.x) * VEC, V, vec_ok, e, id);
+  float hv, mv;
+  int hi, mi;
+  sel_head(e, id, hv, hi);
+  mv = hv; mi = hi;
+  sel_block_best<SMP_WAVES>(mv, mi, s_v, s_i, 0);
   const size_t pc = (size_t)row * CH + chunk;
   if (K == 0) {
     // the chunk's max logit and its sum of exp(z - z_max), z = x * inv_temp (rounded as stage 2 rounds it)
-    const float zm = mv * inv_temp;
-    float se = 0.0f;
-#pragma unroll
-    for (int u = 0; u < VEC; u++) se += (id[u] != SMP_NONE) ? expf(e[u] * inv_temp - zm) : 0.0f;
-    se = wave_sum(se);
-    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = se;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float t = 0.0f;
-#pragma unroll
-      for (int w = 0; w < SMP_WAVES; w++) t += s_sum[w];
-      pmax[pc] = mv;
-      psum[pc] = t;
-    }
+    const float se = sel_chunk_expsum(e, id, inv_temp, mv * inv_temp, s_sum);
+    if (threadIdx.x == 0) { pmax[pc] = mv; psum[pc] = se; }
     return;
   }
-  // top K of the chunk in rank order: round 0's winner is the max found above
-  for (int k = 0; k < K; k++) {
-    float bv = hv;
-    int bi = hi;
-    if (k > 0) smp_block_best(bv, bi, s_v, s_i, k);
-    else { bv = mv; bi = mi; }
-    if (threadIdx.x == 0) { ptv[pc * SMP_KMAX + k] = bv; pti[pc * SMP_KMAX + k] = bi; }
-    if (bi == hi && bi != SMP_NONE) {        // the owner drops the element and finds its next head
-#pragma unroll
-      for (int u = 0; u < VEC; u++)
-        if (id[u] == bi) { id[u] = SMP_NONE; e[u] = -INFINITY; }
-      hv = -INFINITY; hi = SMP_NONE;
-#pragma unroll
-      for (int u = 0; u < VEC; u++)
-        if (smp_better(e[u], id[u], hv, hi)) { hv = e[u]; hi = id[u]; }
-    }
-  }
+  sel_chunk_topk(K, e, id, hv, hi, mv, mi, s_v, s_i, ptv, pti, pc, SMP_KMAX);
 }
 
 // the uniform of (seed, step t, row r): 24 bits, stateless
@@ -178,7 +106,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_draw_kernel(int V, int CH,
   const float inv_temp = ctl->inv_temp, top_p = ctl->top_p;
   const float u01 = smp_uniform(ctl->seed, t, rows, row);
   const T* r = x + (size_t)row * ldx;
-  int tok = SMP_NONE;
+  int tok = SEL_NONE;
   float logp = 0.0f;
   if (K == 0) {
     // row max, W and the chunk that holds u * W: every thread walks the <= 64 chunk partials in chunk order
@@ -200,12 +128,12 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_draw_kernel(int V, int CH,
     // inclusive scan of exp(z - m) over the chunk's elements in index order
     float e[VEC];
     int id[VEC];
-    smp_load<T, VEC>(r, cs * CHUNK + threadIdx.x * VEC, V, vec_ok, e, id);
+    sel_chunk_load<T, VEC>(r, cs * CHUNK + threadIdx.x * VEC, V, vec_ok, e, id);
     float pre[VEC];
     float tt = 0.0f;
 #pragma unroll
     for (int q = 0; q < VEC; q++) {
-      tt += (id[q] != SMP_NONE) ? expf(e[q] * inv_temp - m) : 0.0f;
+      tt += (id[q] != SEL_NONE) ? expf(e[q] * inv_temp - m) : 0.0f;
       pre[q] = tt;
     }
     const float inc = smp_wave_scan(tt, lane);
@@ -213,10 +141,10 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_draw_kernel(int V, int CH,
     __syncthreads();
     float off = inc - tt;
     for (int w = 0; w < wv; w++) off += s_tot[w];
-    int first = SMP_NONE;
+    int first = SEL_NONE;
 #pragma unroll
     for (int q = VEC - 1; q >= 0; q--)
-      if (id[q] != SMP_NONE && off + pre[q] > rem) first = id[q];
+      if (id[q] != SEL_NONE && off + pre[q] > rem) first = id[q];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) first = min(first, __shfl_xor(first, o));
     if (lane == 0) s_first[wv] = first;
@@ -225,7 +153,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_draw_kernel(int V, int CH,
     first = s_first[0];
 #pragma unroll
     for (int w = 1; w < SMP_WAVES; w++) first = min(first, s_first[w]);
-    tok = first != SMP_NONE ? first : min(V, (cs + 1) * CHUNK) - 1;       // rounding left none: the chunk's last element
+    tok = first != SEL_NONE ? first : min(V, (cs + 1) * CHUNK) - 1;       // rounding left none: the chunk's last element
     logp = to_f<T>(r[tok]) * inv_temp - m - logf(W);
   } else {
     const size_t base = (size_t)row * CH * SMP_KMAX;
@@ -239,21 +167,21 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_draw_kernel(int V, int CH,
     // K-way merge of the sorted chunk lists: lane c holds the head of chunk c's list, lane r keeps the rank-r winner
     int h = 0;
     float cv = lane < CH ? s_cv[lane * K] : -INFINITY;
-    int ci = lane < CH ? s_ci[lane * K] : SMP_NONE;
+    int ci = lane < CH ? s_ci[lane * K] : SEL_NONE;
     float myv = -INFINITY;
-    int myi = SMP_NONE;
+    int myi = SEL_NONE;
     for (int k = 0; k < K; k++) {
       float bv = cv;
       int bi = ci;
-      smp_wave_best(bv, bi);
+      sel_wave_best(bv, bi);
       if (lane == k) { myv = bv; myi = bi; }
-      if (bi == ci && bi != SMP_NONE) {
+      if (bi == ci && bi != SEL_NONE) {
         h++;
         cv = h < K ? s_cv[lane * K + h] : -INFINITY;
-        ci = h < K ? s_ci[lane * K + h] : SMP_NONE;
+        ci = h < K ? s_ci[lane * K + h] : SEL_NONE;
       }
     }
-    const bool cand = lane < K && myi != SMP_NONE;
+    const bool cand = lane < K && myi != SEL_NONE;
     const float z = cand ? myv * inv_temp : -INFINITY;
     const float m = wave_max(z);
     const float w = cand ? expf(z - m) : 0.0f;
@@ -272,64 +200,50 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_draw_kernel(int V, int CH,
     if (lane != 0) return;
   }
   // one thread per row from here
-  if (tok == SMP_NONE || tok < 0 || tok >= V) tok = 0;      // (only a row without a finite logit gets here)
+  if (tok == SEL_NONE || tok < 0 || tok >= V) tok = 0;      // (only a row without a finite logit gets here)
   out[(size_t)row * out_stride] = tok;
   step_logp[row] = logp;
   seq_logp[row] += logp;
-  // the greedy kernel's bookkeeping: sticky per-row end flag; the row that completes the set records the step
-  if ((int64_t)tok == end_id) {
-    ended[row] = 1;
-    if (atomicAdd(ended_count, 1) + 1 == rows) atomicMin(all_ended_at, (unsigned long long)t);
-  }
+  if ((int64_t)tok == end_id) sel_mark_ended(&ended[row], 1, ended_count, rows, all_ended_at, t);
 }
 
 }  // namespace vct
 using namespace vct;
 
-static bool dt_ok_smp(int dt) { return dt == VCT_F32 || dt == VCT_BF16; }
-
-static int64_t smp_chunks(int dtype, int V) {
-  const int chunk = SMP_THREADS * (dtype == VCT_BF16 ? 8 : 4);
-  return ((int64_t)V + chunk - 1) / chunk;
-}
-
 extern "C" int64_t vct_sample_select_workspace_bytes(int dtype, int rows, int V) {
-  if (!dt_ok_smp(dtype) || rows < 1 || V < 1) return 0;
-  return (int64_t)rows * smp_chunks(dtype, V) * (2 + 2 * SMP_KMAX) * 4;
+  if (!dt_ok(dtype) || rows < 1 || V < 1) return 0;
+  return (int64_t)rows * sel_chunks(dtype, V) * (2 + 2 * SMP_KMAX) * 4;
 }
 
-extern "C" int vct_sample_select(const vct_sample_select_desc* d, void* stream) {
-  if (!d || !dt_ok_smp(d->dtype) || !d->x || !d->out || !d->ended || !d->ended_count || !d->all_ended_at || !d->step_logp ||
-      !d->seq_logp || !d->ctl || !d->workspace)
-    return VCT_E_ARG;
+template <typename T>
+static void sample_launch(const vct_sample_select_desc* d, int CH, hipStream_t st) {
   const int rows = d->rows, V = d->V;
-  if (rows < 1 || V < 1 || d->ldx < V || d->out_stride <= 0 || d->t < 0) return VCT_E_SHAPE;
-  const int64_t CH = smp_chunks(d->dtype, V);
-  if (CH > SMP_CHMAX) return VCT_E_SHAPE;                         // one chunk list per lane of the merging wave
-  if ((((uintptr_t)d->ctl) & 15) != 0 || (((uintptr_t)d->workspace) & 15) != 0) return VCT_E_ALIGN;
-  if (d->workspace_bytes < vct_sample_select_workspace_bytes(d->dtype, rows, V)) return VCT_E_WORKSPACE;
   const size_t MC = (size_t)rows * (size_t)CH;
   float* pmax = (float*)d->workspace;
   float* psum = pmax + MC;
   float* ptv = psum + MC;
   int* pti = (int*)(ptv + MC * SMP_KMAX);
-  const size_t es = d->dtype == VCT_BF16 ? 2 : 4;
-  const bool vec_ok = (((uintptr_t)d->x) & 15) == 0 && (((size_t)d->ldx * es) & 15) == 0;
-  hipStream_t st = (hipStream_t)stream;
+  const bool vec_ok = (((uintptr_t)d->x) & 15) == 0 && (((size_t)d->ldx * sizeof(T)) & 15) == 0;
   unsigned long long* at = reinterpret_cast<unsigned long long*>(d->all_ended_at);
-  if (d->dtype == VCT_BF16) {
-    vct::launch((sample_partial_kernel<bf16_t>), dim3(rows, (unsigned)CH), dim3(SMP_THREADS), 0, st, V, (const bf16_t*)d->x, d->ldx,
-                vec_ok, (const uint8_t*)d->ended, d->ctl, pmax, psum, ptv, pti);
-    vct::launch((sample_draw_kernel<bf16_t>), dim3(rows), dim3(SMP_THREADS), 0, st, V, (int)CH, (const bf16_t*)d->x, d->ldx, vec_ok,
-                d->ctl, (const float*)pmax, (const float*)psum, (const float*)ptv, (const int*)pti, d->out, d->out_stride, d->end_id,
-                d->pad_id, d->ended, d->ended_count, at, d->step_logp, d->seq_logp, (int)d->t);
-  } else {
-    vct::launch((sample_partial_kernel<float>), dim3(rows, (unsigned)CH), dim3(SMP_THREADS), 0, st, V, (const float*)d->x, d->ldx,
-                vec_ok, (const uint8_t*)d->ended, d->ctl, pmax, psum, ptv, pti);
-    vct::launch((sample_draw_kernel<float>), dim3(rows), dim3(SMP_THREADS), 0, st, V, (int)CH, (const float*)d->x, d->ldx, vec_ok,
-                d->ctl, (const float*)pmax, (const float*)psum, (const float*)ptv, (const int*)pti, d->out, d->out_stride, d->end_id,
-                d->pad_id, d->ended, d->ended_count, at, d->step_logp, d->seq_logp, (int)d->t);
-  }
+  vct::launch((sample_partial_kernel<T>), dim3(rows, (unsigned)CH), dim3(SMP_THREADS), 0, st, V, (const T*)d->x, d->ldx, vec_ok,
+              (const uint8_t*)d->ended, d->ctl, pmax, psum, ptv, pti);
+  vct::launch((sample_draw_kernel<T>), dim3(rows), dim3(SMP_THREADS), 0, st, V, CH, (const T*)d->x, d->ldx, vec_ok, d->ctl,
+              (const float*)pmax, (const float*)psum, (const float*)ptv, (const int*)pti, d->out, d->out_stride, d->end_id, d->pad_id,
+              d->ended, d->ended_count, at, d->step_logp, d->seq_logp, (int)d->t);
+}
+
+extern "C" int vct_sample_select(const vct_sample_select_desc* d, void* stream) {
+  if (!d || !dt_ok(d->dtype) || !d->x || !d->out || !d->ended || !d->ended_count || !d->all_ended_at || !d->step_logp ||
+      !d->seq_logp || !d->ctl || !d->workspace)
+    return VCT_E_ARG;
+  const int rows = d->rows, V = d->V;
+  if (rows < 1 || V < 1 || d->ldx < V || d->out_stride <= 0 || d->t < 0) return VCT_E_SHAPE;
+  const int64_t CH = sel_chunks(d->dtype, V);
+  if (CH > SMP_CHMAX) return VCT_E_SHAPE;                         // one chunk list per lane of the merging wave
+  if ((((uintptr_t)d->ctl) & 15) != 0 || (((uintptr_t)d->workspace) & 15) != 0) return VCT_E_ALIGN;
+  if (d->workspace_bytes < vct_sample_select_workspace_bytes(d->dtype, rows, V)) return VCT_E_WORKSPACE;
+  if (d->dtype == VCT_BF16) sample_launch<bf16_t>(d, (int)CH, (hipStream_t)stream);
+  else sample_launch<float>(d, (int)CH, (hipStream_t)stream);
   VCT_CHECK_LAUNCH();
   return VCT_OK;
 }

@@ -1,5 +1,6 @@
 """Caption decoding: greedy / beam / sampled selection and the KV-cached decode-step kernels (csrc/vct_decode.hip,
-csrc/vct_decode_block.hip, csrc/vct_beam.hip, csrc/vct_sample.hip, csrc/vct_logit_controls.hip, csrc/vct_ensemble.hip)."""
+csrc/vct_decode_block.hip, csrc/vct_select.hip, csrc/vct_beam.hip, csrc/vct_sample.hip over csrc/vct_select_core.h,
+csrc/vct_logit_controls.hip, csrc/vct_ensemble.hip)."""
 import torch
 
 from .. import _lib as L
@@ -38,8 +39,11 @@ def beam_reorder(src, dst, parent, M: int, Lmax: int, d: int, t: int):
 
 def sample_select_workspace_bytes(dtype, rows: int, V: int) -> int:
     """Workspace of vct_sample_select (include/vct_hip.h): chunk partials of every row, sized for the largest k (64)."""
-    chunk = 256 * (8 if dtype == torch.bfloat16 else 4)
-    return rows * ((V + chunk - 1) // chunk) * (2 + 2 * 64) * 4
+    n = int(L.load().vct_sample_select_workspace_bytes(L.dtype_code(dtype), int(rows), int(V)))
+    if n <= 0:
+        raise ValueError(f"sample_select: {rows} rows x {V} columns of {dtype} is outside the kernels' range "
+                         f"(fp32 or bf16, at least one row and one column)")
+    return n
 
 
 def sample_select(x, out, end_id: int, pad_id: int, ended, ended_count, all_ended_at, t: int, step_logp, seq_logp, ctl, ws, cols=None):
